@@ -15,6 +15,13 @@ separate region of >= 20 mcmc_step calls (each with its pmove all-reduce and hos
 SURVEY.md §8d).  Multi-GPU: weak scaling, walkers sharded, one all-reduce of 16 floats
 per step.  ``--gpus N`` without a torchrun environment starts N rank processes itself
 (one GPU each, RCCL) before anything touches the GPU; rank 0 prints the line.
+
+A plain run does what ``value`` needs and no more: set-up, burn-in, warmup, the timed steps,
+the result line.  ``--full`` adds every other measurement (the per-kernel HIP-event region and
+the roofline, the MCMC-only / E_L-only rates, the C4 / C5 lines, the CPU baseline), each with
+the switches it always had.  ``--dump-outputs DIR`` writes what the last timed step returned
+(walkers, local energies, observables, accept counts, reduced statistics) as DIR/<name>.npy;
+every input is seeded, so two builds run with the same arguments compare array for array.
 """
 
 from __future__ import annotations
@@ -48,6 +55,13 @@ def parse():
     ap.add_argument("--flux", type=int, default=15)
     ap.add_argument("--mcmc-steps", type=int, default=10)
     ap.add_argument("--burn-in", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: per-kernel events and roofline, "
+                    "MCMC-only / E_L-only timings, the extra configs and the CPU baseline (each still has "
+                    "its own --no-... switch); without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                    "at most 64 MB in all: a fixed seeded sample of rows beyond that)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-components", action="store_true",
@@ -66,7 +80,11 @@ def parse():
     ap.add_argument("--extra-warmup", type=int, default=2)
     ap.add_argument("--cpu-c1-seconds", type=float, default=6.0,
                     help="CPU-baseline budget for BASELINE.json configs[0] (N=3 2Q=2, B=100)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps only
+        args.no_cpu_baseline = args.no_components = args.no_kernel_events = True
+        args.extra_configs = ""
+    return args
 
 
 def spawn_ranks(n: int) -> int:
@@ -92,12 +110,34 @@ def spawn_ranks(n: int) -> int:
 
 
 EXTRA_CONFIGS = {"C4": ((10, 0), 23), "C5": ((20, 0), 57)}  # BASELINE.json configs[3], [4]
+DUMP_BUDGET_BYTES = 64 * 2**20
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: each array as DIR/<name>.npy (DIR/<name>.rank<r>.npy with several ranks),
+    float32 or float64.  The 64 MB are shared equally between the arrays and the ranks; a larger
+    array keeps a fixed seeded sample of its rows (sorted, so the file stays in walker order)."""
+    import numpy as np
+
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (len(arrays) * world)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64 if a.dtype.itemsize > 4 else np.float32)
+        if a.nbytes > share:
+            rows = a.shape[0]
+            keep = max(1, share // (a.nbytes // rows))
+            a = a[np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))]
+        np.save(out / (f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"), a)
 
 
 def run_workload(args, dev, rank, world, nspins, flux, B, n_steps, n_warmup, burn_in, instrument, components,
-                 mcmc_calls=None):
+                 mcmc_calls=None, dump=None):
     """One workload: burn-in, W warmup VMC steps, exactly K timed steps (barrier + sync on both
-    sides, max over ranks), then the instrumented region and the component timings."""
+    sides, max over ranks), the output dump if asked for, then the instrumented region and the
+    component timings."""
     from deephall_amd import _lib, config
     from deephall_amd.hamiltonian import _run_local_energy
     from deephall_amd.loss import device_stats, reduce_stats
@@ -125,10 +165,12 @@ def run_workload(args, dev, rank, world, nspins, flux, B, n_steps, n_warmup, bur
 
     pmoves = np.zeros(100)
     t_iter = [0]
+    last = {}  # the per-walker outputs of the latest step (references only), for --dump-outputs
 
     def vmc_step(data, key, it=iteration):
         nonlocal width, pmoves
         data, e_l, obs, n_accept = it(params, data, key, width)
+        last["e_l"], last["obs"], last["n_accept"] = e_l, obs, n_accept
         local_stats = device_stats(model, e_l, obs, n_accept, steps)
         stats = reduce_stats(local_stats)  # the one all-reduce of the step
         # host side of the reference loop: width adaptation reads pmove (a device sync,
@@ -164,6 +206,11 @@ def run_workload(args, dev, rank, world, nspins, flux, B, n_steps, n_warmup, bur
     dt = float(t.item())
     energy = complex(stats["energy"].item())
     pmove = float(stats["pmove"].item())
+    if dump and n_steps > 0:
+        # what a caller of the timed step holds after the last one: the walkers, E_L [B,2] (re, im),
+        # the observables [B,8], the accept counts [B] and the reduced statistics (re, im of each, by name)
+        flat = torch.stack([torch.view_as_real(stats[k].to(torch.complex128)) for k in sorted(stats)]).reshape(-1)
+        dump_outputs(dump, dict(walkers=data, stats=flat, **last), rank, world)
 
     # ---------------- instrumented region: the same K steps again with a HIP event pair
     # around every kernel launch (on the launch stream), for the per-kernel breakdown and
@@ -304,7 +351,7 @@ def main():
     B = args.batch
     N = sum(args.nspins)
     r = run_workload(args, dev, rank, world, tuple(args.nspins), args.flux, B, args.steps, args.warmup,
-                     args.burn_in, not args.no_kernel_events, not args.no_components)
+                     args.burn_in, not args.no_kernel_events, not args.no_components, dump=args.dump_outputs)
     dt, dt_prof, prof, t_mcmc, t_el = r["dt"], r["dt_prof"], r["prof"], r["t_mcmc"], r["t_el"]
     energy, pmove = r["energy"], r["pmove"]
     steps = args.mcmc_steps

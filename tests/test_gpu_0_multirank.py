@@ -68,7 +68,7 @@ def test_bench_launches_its_own_ranks():
     _gpu_or_skip()
     env = dict(os.environ, DH_BENCH_ONE_GPU="1", DH_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--burn-in", "0", "--batch", "256", "--mcmc-calls", "2", "--no-cpu-baseline",
+                          "--burn-in", "0", "--batch", "256", "--full", "--mcmc-calls", "2", "--no-cpu-baseline",
                           "--no-kernel-events"], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

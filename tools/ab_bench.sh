@@ -7,7 +7,7 @@ mkdir -p gpurun_out/ab
 R=${ROUNDS:-2}
 for i in $(seq 1 $R); do
   for v in old new; do
-    DH_LIB_PATH=ab/$v.so timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 $BENCH_ARGS \
+    DH_LIB_PATH=ab/$v.so timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 $BENCH_ARGS \
       > gpurun_out/ab/${v}_$i.json 2> gpurun_out/ab/${v}_$i.err
     echo "$v $i done"
   done
