@@ -733,10 +733,7 @@ int run_trunk(dh_handle* h, const float* x, int nw, int C, const Work& w, hipStr
   // the 2320-column orbital map as its last pass (C5 73.5 -> 74.2 K E_L/s, 2.53 -> 2.59 M
   // walker-steps/s same box, profiles/r06_v35_chain_big20_ab.txt)
   const bool chain_any = C == 1 && x6 && ln_fused && D == 256;
-  auto chain_at = [&](int l) {
-    (void)l;
-    return chain_any && (rows < 65536 || d.N >= 20);
-  };
+  auto chain_at = [&]() { return chain_any && (rows < 65536 || d.N >= 20); };
   // local energy, split-bf16, D = 256, N <= 8: GEMM + channel LayerNorm fused per map
   const bool lnch = C > 1 && x6 && C == 2 * d.N + 5 && h->gemm_mode != DH_GEMM_X6_ALL_UNFUSED &&
                     gemm_lnch_supported(d.N, D);
@@ -756,8 +753,8 @@ int run_trunk(dh_handle* h, const float* x, int nw, int C, const Work& w, hipStr
   }
   for (int l = 0; l < d.L; ++l) {
     const LayerParams& lp = P.layer[l];
-    const bool chain = chain_at(l);
-    if (l > 0 && !chain_at(l - 1))  // (a chained layer's last pass wrote this layer's q|k|v)
+    const bool chain = chain_at();
+    if (l > 0 && !chain_at())  // (a chained layer's last pass wrote this layer's q|k|v)
       gemm(w.h, D, lp.Wqkv, lp.WqkvT, lp.WqkvP, 3 * D, lp.bqkv, nullptr, 0, w.qkv, 3 * D, 3 * D, D);
     // log psi, chain form: layer 1's attention runs in the chain kernel's prologue (its o
     // never leaves the CU; attn_val.h)
@@ -858,7 +855,7 @@ int run_trunk(dh_handle* h, const float* x, int nw, int C, const Work& w, hipStr
     }
   }
   // (the envelope-first local energy maps only six special rows per electron, det.hip)
-  if ((d.L == 0 || !chain_at(d.L - 1)) && !(C > 1 && env_first(d)))
+  if ((d.L == 0 || !chain_at()) && !(C > 1 && env_first(d)))
     gemm(w.h, D, P.Worb, P.WorbT, P.WorbP, d.ld_orb, P.borb, nullptr, 0, w.F, d.ld_orb, d.orb_cols, D);
   return check_launch();
 }
@@ -1693,19 +1690,25 @@ size_t dh_debug_f_offset(const dh_handle* h, int B, int op) {
   return (size_t)(w.F - reinterpret_cast<float*>(size_t(64)));
 }
 
-// Test hook: one GEMM launch of kernel variant `variant` (-1 = default).
+// Test hook: one GEMM launch of kernel variant `variant` (the codes of launch_gemm_variant, or
+// 100 + a code of launch_gemm_nt_variant; -1 = code 0).  The launchers check
+// the code before they touch an argument.
 int dh_debug_gemm(int variant, const float* X, int ldx, const float* W, int ldw, const float* bias, const float* R,
                   int ldr, float* Y, int ldy, int rows, int ncols, int K, int C, void* stream) {
+  bool known = true;
   if (variant >= 100) {
     if (K % 32 != 0) return fail(DH_EINVAL, "NT GEMM needs K % 32 == 0");
-    launch_gemm_nt_variant(variant - 100, X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C,
-                           (hipStream_t)stream);
+    known = launch_gemm_nt_variant(variant - 100, X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C,
+                                   (hipStream_t)stream);
   } else {
-    launch_gemm_variant(variant < 0 ? 0 : variant, X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C,
-                        (hipStream_t)stream);
+    known = launch_gemm_variant(variant < 0 ? 0 : variant, X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C,
+                                (hipStream_t)stream);
   }
+  if (!known) return fail(DH_EINVAL, "no GEMM variant " + std::to_string(variant));
   return check_launch();
 }
+
+int dh_debug_gemm_x6_choice(int rows, int ncols) { return gemm_x6_choose(rows, ncols); }
 
 int dh_debug_x6_plane_rows(int ncols) { return x6_plane_rows(ncols); }
 
@@ -1719,10 +1722,9 @@ int dh_debug_gemm_x6(int variant, const float* X, int ldx, const uint16_t* Wp, i
                      const float* R, int ldr, float* Y, int ldy, int rows, int ncols, int K, int C, void* stream) {
   if (!gemm_x6_supported(K) || ldp < x6_plane_rows(ncols)) return fail(DH_EINVAL, "bad gemm_x6 args");
   if (variant >= 10 && K > 256) return fail(DH_EINVAL, "persistent gemm_x6 needs K <= 256");
-  if (variant < 0)
-    launch_gemm_x6(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, (hipStream_t)stream);
-  else
-    launch_gemm_x6_variant(variant, X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, (hipStream_t)stream);
+  if (variant < 0) variant = gemm_x6_choose(rows, ncols);
+  if (!launch_gemm_x6_variant(variant, X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, (hipStream_t)stream))
+    return fail(DH_EINVAL, "no gemm_x6 variant " + std::to_string(variant));
   return check_launch();
 }
 
@@ -1730,7 +1732,8 @@ int dh_debug_gemm_x6_ln(int mode, int nw, const float* X, int ldx, const uint16_
                         const float* ln, float* h, int rows, int K, void* stream) {
   if (!gemm_x6_supported(K) || K > 256 || ldp < x6_plane_rows(256) || rows < 1 || (mode != 0 && mode != 1))
     return fail(DH_EINVAL, "bad gemm_x6_ln args");
-  launch_gemm_x6_ln(X, ldx, Wp, ldp, bias, ln, h, rows, K, mode, nw, (hipStream_t)stream);
+  if (!launch_gemm_x6_ln(X, ldx, Wp, ldp, bias, ln, h, rows, K, mode, nw, (hipStream_t)stream))
+    return fail(DH_EINVAL, "no gemm_x6_ln form " + std::to_string(nw));
   return check_launch();
 }
 

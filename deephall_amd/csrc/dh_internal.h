@@ -89,13 +89,16 @@ inline void ensure_smem(Kern kernel, size_t bytes) {
 // gemm.hip: Y[r][n] = sum_k X[r][k] W[k][n] + (r % C == 0 ? bias[n] : 0) + (R ? R[r][n] : 0)
 void launch_gemm(const float* X, int ldx, const float* W, int ldw, const float* bias, const float* R, int ldr,
                  float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s);
-void launch_gemm_variant(int v, const float* X, int ldx, const float* W, int ldw, const float* bias, const float* R,
+// One tile form by its code (0 .. 11 but 3; launch_gemm picks 9, 10); false, nothing launched,
+// for any other code.
+bool launch_gemm_variant(int v, const float* X, int ldx, const float* W, int ldw, const float* bias, const float* R,
                          int ldr, float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s);
 // NT form: Y = X Wt^T, Wt[n][k] (row stride ldw), K % 32 == 0, Wt rows padded to 256.
-void launch_gemm_nt_variant(int v, const float* X, int ldx, const float* Wt, int ldw, const float* bias,
+// Codes 0 .. 7, three-stage 10, 11, 14 .. 17, persistent 20 .. 26 (launch_gemm_nt picks 4, 6, 7,
+// 20, 25); false, nothing launched, for any other code.
+bool launch_gemm_nt_variant(int v, const float* X, int ldx, const float* Wt, int ldw, const float* bias,
                             const float* R, int ldr, float* Y, int ldy, int rows, int ncols, int K, int C,
                             hipStream_t s);
-void set_gemm_variant(int v);
 // NT GEMM with the tile shape chosen from (rows, ncols, residual): Wt[n][k], row stride ldw.
 void launch_gemm_nt(const float* X, int ldx, const float* Wt, int ldw, const float* bias, const float* R, int ldr,
                     float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s);
@@ -110,13 +113,30 @@ void launch_gemm_ln(const float* X, int ldx, const float* Wt, int ldw, const flo
 int x6_plane_rows(int ncols);
 void launch_split_planes(const float* Wt, int ldw, int ncols, int K, uint16_t* Wp, hipStream_t s);
 bool gemm_x6_supported(int K);
-void launch_gemm_x6_variant(int v, const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias,
+// The forms launch_gemm_x6 picks from, named kernel_tile (rows x columns); the values are the
+// variant codes of DESIGN.md and profiles/.
+enum X6Form : int {
+  X6D_128x192 = 44,  // gemm_x6d: two workgroups per CU, short (log-psi) row counts
+  X6D_256x128 = 46,
+  X6Q_256x128 = 52,  // gemm_x6q: persistent, channel rows
+  X6Q_256x256 = 56,
+  X6Q_256x192 = 57,
+  X6Q_256x160 = 58,
+  X6M_256x256 = 76,  // gemm_x6m: persistent 16x16x32 form, the wide channel-row maps
+  X6M_256x192 = 77,
+};
+// The form launch_gemm_x6 takes for a shape (host only: no device call).
+int gemm_x6_choose(int rows, int ncols);
+// One form by its code: an X6Form, or one of the tiles kept beside them for comparison (gemm_x6.hip
+// kX6Forms); false, nothing launched, for any other code.
+bool launch_gemm_x6_variant(int v, const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias,
                             const float* R, int ldr, float* Y, int ldy, int rows, int ncols, int K, int C,
                             hipStream_t s);
 void launch_gemm_x6(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
                     float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s);
 // h = LN(h + X W + b) (mode 0) or LN(h + tanh(X W + b)) (mode 1), in place, split-bf16
-// arithmetic; h [rows][256], ln = [gamma(256), beta(256)]; nw = tile form (0: pick; gemm_x6.hip).
+// arithmetic; h [rows][256], ln = [gamma(256), beta(256)]; nw = tile form (0: pick, or 1, 2, 3, 4, 8;
+// gemm_x6.hip); false, nothing launched, for any other nw.
 // feat (layer 1 of log psi, mode 0): the residual h = features W0 is formed in the epilogue
 // from geo [rows][4] = (sin th, cos th, sin ph, cos ph) and W0 [4][256] instead of read.
 struct X6Feat {
@@ -132,7 +152,7 @@ struct X6Feat {
   const uint16_t* L1V = nullptr;
   const uint16_t* L1B = nullptr;
 };
-void launch_gemm_x6_ln(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* ln,
+bool launch_gemm_x6_ln(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* ln,
                        float* h, int rows, int K, int mode, int nw, hipStream_t s, X6Feat feat = X6Feat{});
 // gemm_lnch.hip: channel rows (C = 2N + 5 per electron, ne electrons), D = K = 256, N <= 8:
 // h = LN_ch(h + X W + b) (mode 0) or LN_ch(h + tanh_ch(h W + b)) (mode 1) in ONE launch,

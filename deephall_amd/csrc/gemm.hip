@@ -712,127 +712,124 @@ void launch_t(const float* X, int ldx, const float* W, int ldw, const float* bia
                      ldr, Y, ldy, rows, ncols, K, C, ntm, ntn);
 }
 
-int g_variant = -1;  // -1: automatic
 }  // namespace
 
 // X must have round_up(rows, 256) readable rows (workspace rows are padded).
-void launch_gemm_variant(int v, const float* X, int ldx, const float* W, int ldw, const float* bias, const float* R,
+bool launch_gemm_variant(int v, const float* X, int ldx, const float* W, int ldw, const float* bias, const float* R,
                          int ldr, float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
   switch (v) {
     case 1:
       launch_t<128, 128, 32, 64, 64>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 2:
       launch_t<128, 256, 16, 64, 128>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 3:
-      launch_t<256, 128, 16, 128, 64>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 4:
       launch_t<64, 128, 16, 32, 64>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 5:
       launch_t<128, 64, 16, 64, 32>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 6:
       launch_t<64, 64, 16, 32, 32>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 7:
       launch_t<128, 64, 32, 64, 32>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 8:
       launch_t<128, 32, 16, 32, 32>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 9:
       launch_t<256, 64, 16, 64, 32>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 10:
       launch_t<128, 64, 16, 32, 64>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 11:
       launch_t<256, 64, 16, 128, 32>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    default:
+      return true;
+    case 0:
       launch_t<128, 128, 16, 64, 64>(X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
+      return true;
+    default:
+      return false;
   }
 }
 
 // NT variants (Wt[n][k]); K % 32 == 0, Wt rows padded to a multiple of 256.
-void launch_gemm_nt_variant(int v, const float* X, int ldx, const float* Wt, int ldw, const float* bias,
+bool launch_gemm_nt_variant(int v, const float* X, int ldx, const float* Wt, int ldw, const float* bias,
                             const float* R, int ldr, float* Y, int ldy, int rows, int ncols, int K, int C,
                             hipStream_t s) {
   switch (v) {
     case 1:
       launch_nt<128, 64, 64, 32>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 2:
       launch_nt<256, 128, 64, 64>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 3:
       launch_nt<128, 256, 64, 64>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 4:
       launch_nt<64, 128, 32, 64>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 5:
       launch_nt<256, 64, 64, 32>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 6:
       launch_nt<128, 128, 32, 64>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 7:
       launch_nt<64, 64, 32, 32>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     // persistent (one DMA ring across the workgroup's tiles; Y padded, see gemm_ntp_kernel)
     case 20:
       launch_ntp<128, 128, 32, 64, 2, 2>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 21:
       launch_ntp<128, 128, 32, 64, 3, 1>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 22:
       launch_ntp<128, 64, 64, 32, 3, 2>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 23:
       launch_ntp<64, 64, 32, 32, 2, 4>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 24:
       launch_ntp<256, 64, 64, 32, 2, 2>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 25:
       launch_ntp<64, 128, 32, 64, 2, 3>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 26:
       launch_ntp<128, 64, 64, 32, 2, 3>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     // three-stage rings
     case 10:
       launch_nt<128, 128, 64, 64, 3>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 11:
       launch_nt<128, 64, 64, 32, 3>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 14:
       launch_nt<64, 128, 32, 64, 3>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 15:
       launch_nt<256, 64, 64, 32, 3>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 16:
       launch_nt<128, 128, 32, 64, 3>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
+      return true;
     case 17:
       launch_nt<64, 64, 32, 32, 3>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 18:
-      launch_nt<256, 128, 64, 64, 3>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    default:
+      return true;
+    case 0:
       launch_nt<128, 128, 64, 64>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
+      return true;
+    default:
+      return false;
   }
 }
-
-void set_gemm_variant(int v) { g_variant = v; }
 
 void launch_gemm_nt(const float* X, int ldx, const float* Wt, int ldw, const float* bias, const float* R, int ldr,
                     float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
@@ -844,9 +841,7 @@ void launch_gemm_nt(const float* X, int ldx, const float* Wt, int ldw, const flo
   // need ldy >= round_up(ncols, 128)).
   int v;
   const bool pad_ok = ldy >= round_up(ncols, 128);
-  if (g_variant >= 100) {
-    v = g_variant - 100;
-  } else if (rows >= 65536) {
+  if (rows >= 65536) {
     v = (ncols % 256 == 0) ? ((R && pad_ok) ? 20 : 6) : 7;
   } else {
     v = (ncols >= 512 && pad_ok) ? 25 : (ncols == 256 ? 4 : 7);
@@ -907,8 +902,7 @@ void launch_gemm(const float* X, int ldx, const float* W, int ldw, const float* 
                  float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
   // measured on MI355X (tools/gemm_bench.py): 256x64 tiles (8 waves of 64x32) win on the
   // channel GEMMs and wide outputs; 128x64 tiles of 32x64 waves on short N=256 log-psi GEMMs
-  int v = g_variant;
-  if (v < 0) v = (rows < 65536 && ncols <= 256) ? 10 : 9;
+  const int v = (rows < 65536 && ncols <= 256) ? 10 : 9;
   launch_gemm_variant(v, X, ldx, W, ldw, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
 }
 

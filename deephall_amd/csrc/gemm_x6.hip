@@ -32,27 +32,6 @@
 #include "dh_internal.h"
 #include "device_common.h"
 
-#ifndef X6M_BIAS1  // A/B knob: gemm_x6m's epilogue bias loads ahead of its stores (1) or between them (0)
-#define X6M_BIAS1 1
-#endif
-#ifndef CHAIN_P3B  // A/B knob: P3 bias loads hoisted ahead of the stores (1) or between them (0)
-#define CHAIN_P3B 1
-#endif
-#ifndef CHAIN_TANH_EXP  // A/B knob: the chain kernel's tanh as 1 - 2 / (exp(2x) + 1) (2 transcendentals + 3 VALU)
-#define CHAIN_TANH_EXP 0
-#endif
-#ifndef CHAIN_LN1P  // A/B knob: the chain kernel's LayerNorms in one statistics round (fast variance)
-#define CHAIN_LN1P 1
-#endif
-#ifndef CHAIN_P3T  // A/B knob: P3 MFMAs with the operands swapped (accumulator = tile row x 32 columns,
-#define CHAIN_P3T 1  // one register = two 128-B row segments: full-rate dword stores) instead of float4
-#endif               // stores of 32 rows x 32 B per instruction (round 5)
-#ifndef CHAIN_LBAR  // A/B knob: the chain kernel's barriers wait for LDS only (lgkmcnt(0) + s_barrier) instead
-#define CHAIN_LBAR 1  // of __syncthreads' vmcnt(0), which also waited for the next GEMM's weight prefetch (round 5)
-#endif
-#ifndef X6M_NT  // A/B knob: gemm_x6m's output tiles stored nontemporal (streaming) instead of plain stores
-#define X6M_NT 0
-#endif
 #ifndef CHAIN_STAMP  // diagnostic builds only (tools/chain_stamp.py): per-tile phase stamps of chain_x6s
 #define CHAIN_STAMP 0
 #endif
@@ -165,489 +144,12 @@ __device__ __forceinline__ void ktile_pipelined(const char* Bs, const char* Bn, 
   }
 }
 
-// One wave = 32 rows x (32*TN) columns; NW waves stacked along rows (BM = 32*NW).
-template <int NW, int TN, bool HAS_R>
-__global__ __launch_bounds__(NW * 64) void gemm_x6_kernel(const float* __restrict__ X, int ldx,
-                                                          const uint16_t* __restrict__ Wp, int ldp,
-                                                          const float* __restrict__ bias, const float* R, int ldr,
-                                                          float* Y, int ldy, int rows, int ncols, int K, int C,
-                                                          int ntm, int ntn) {
-  constexpr int BM = 32 * NW, BN = 32 * TN, BK = X6_BK;
-  constexpr int A_BYTES = BM * BK * 4, B_PLANE = BN * BK * 2, STAGE = A_BYTES + 3 * B_PLANE;
-  constexpr int IA = BM / 8, IBP = BN / 16, IB = 3 * IBP;  // DMA wave-instructions (1 KiB each)
-  constexpr int PER = (IA + IB + NW - 1) / NW;
-  constexpr bool PREF = HAS_R && TN <= 4;  // residual prefetched into registers (wider tiles would spill)
-  extern __shared__ float4 smem4[];
-  char* smem = reinterpret_cast<char*>(smem4);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l32 = lane & 31, lh = lane >> 5;
-
-  // XCD-aware tile order (as gemm_nt_kernel): consecutive tiles of a row panel share an XCD
-  const int nblk = ntm * ntn;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk / 8, r8 = nblk % 8, xcd = bid % 8, slot = bid / 8;
-    bid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + slot;
-  }
-  const int tm = bid / ntn, tn = bid % ntn;
-  const int row0 = tm * BM, col0 = tn * BN;
-  const size_t plane = (size_t)ldp * K;  // elements per weight plane
-
-  const uint32_t lds0 = (uint32_t)(size_t)((__attribute__((address_space(3))) char*)smem);
-  auto stage = [&](int k0, int buf) {
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-      const int j = wid + t * NW;  // wave-uniform
-      if ((IA + IB) % NW != 0 && j >= IA + IB) break;
-      const void* src;
-      uint32_t dst;
-      if (j < IA) {  // 8 rows x 128 B of f32 activations
-        const int r = j * 8 + (lane >> 3);
-        const int sl = ((lane & 7) ^ ((r >> 1) & 7)) * 4;
-        src = X + (size_t)(row0 + r) * ldx + k0 + sl;
-        dst = lds0 + (uint32_t)(buf * STAGE + j * 8 * BK * 4);
-      } else {  // 16 rows x 64 B of one bf16 weight plane
-        const int jb = j - IA, p = jb / IBP, rg = (jb % IBP) * 16;
-        const int r = rg + (lane >> 2);
-        const int sl = ((lane & 3) ^ ((r >> 2) & 3)) * 8;
-        src = Wp + p * plane + (size_t)(col0 + r) * K + k0 + sl;
-        dst = lds0 + (uint32_t)(buf * STAGE + A_BYTES + p * B_PLANE + rg * BK * 2);
-      }
-      dst = __builtin_amdgcn_readfirstlane(dst);
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep)
-                   : "v"(src), "s"(dst)
-                   : "memory");
-    }
-  };
-
-  f32x16 acc[TN];
-#pragma unroll
-  for (int b = 0; b < TN; ++b)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[b][e] = 0.f;
-  float rres[PREF ? TN : 1][16];
-
-  const int nk = K / BK;
-  stage(0, 0);
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kt + 1 < nk) stage((kt + 1) * BK, cur ^ 1);
-    if (PREF && kt + 1 == nk) {  // residual loads overlap the last k-tile's MFMAs
-#pragma unroll
-      for (int ni = 0; ni < TN; ++ni) {
-        const int c = col0 + ni * 32 + l32;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int r = row0 + wid * 32 + 4 * lh + (e & 3) + 8 * (e >> 2);
-          rres[ni][e] = (c < ncols && r < rows) ? R[(size_t)r * ldr + c] : 0.f;
-        }
-      }
-    }
-    const char* As = smem + cur * STAGE;
-    const char* Bs = As + A_BYTES;
-#pragma unroll
-    for (int ch = 0; ch < BK / 16; ++ch) {
-      // A fragment: row m, k = 16 ch + 8 lh + (0..7) = logical slots 4ch + 2lh, +1
-      const int m = wid * 32 + l32;
-      const int s0 = 4 * ch + 2 * lh;
-      const float* arow = reinterpret_cast<const float*>(As) + m * BK;
-      const float4 u = *reinterpret_cast<const float4*>(arow + ((s0 ^ ((m >> 1) & 7)) * 4));
-      const float4 v = *reinterpret_cast<const float4*>(arow + (((s0 + 1) ^ ((m >> 1) & 7)) * 4));
-      bf16x8 a0, a1, a2;
-      split3(u, v, a0, a1, a2);
-      const int sb = 2 * ch + lh;  // B fragment: k = 16 ch + 8 lh + (0..7) = slot sb of a 64-B row
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = j * 32 + l32;
-        const int off = n * BK * 2 + ((sb ^ ((n >> 2) & 3)) * 16);
-        const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(Bs + off);
-        const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(Bs + B_PLANE + off);
-        const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(Bs + 2 * B_PLANE + off);
-        // smallest terms first
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[j], 0, 0, 0);
-      }
-    }
-  }
-
-  // Epilogue. C/D map of 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
-  const int rbase = row0 + wid * 32 + 4 * lh;
-  const int rm0 = (C == 1) ? 0 : rbase % C;
-#pragma unroll
-  for (int ni = 0; ni < TN; ++ni) {
-    const int c = col0 + ni * 32 + l32;
-    if (c >= ncols) continue;
-    const float bv = bias ? bias[c] : 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int off = (e & 3) + 8 * (e >> 2);
-      const int r = rbase + off;
-      if (r >= rows) continue;
-      float v = acc[ni][e];
-      if (bias) {
-        bool val = true;
-        if (C > 1) {
-          int t = rm0 + off;
-          while (t >= C) t -= C;
-          val = (t == 0);
-        }
-        if (val) v += bv;
-      }
-      if (PREF) v += rres[PREF ? ni : 0][e];
-      else if (HAS_R) v += R[(size_t)r * ldr + c];
-      Y[(size_t)r * ldy + c] = v;
-    }
-  }
-}
-
-template <int NW, int TN>
-void launch_x6_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
-                 float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
-  constexpr int BM = 32 * NW, BN = 32 * TN;
-  const int ntm = (rows + BM - 1) / BM, ntn = (ncols + BN - 1) / BN;
-  const size_t smem = 2ull * (BM * X6_BK * 4 + 3 * BN * X6_BK * 2);
-  if (R) {
-    ensure_smem(gemm_x6_kernel<NW, TN, true>, smem);
-    hipLaunchKernelGGL((gemm_x6_kernel<NW, TN, true>), dim3(ntm * ntn), dim3(NW * 64), smem, s, X, ldx, Wp, ldp, bias,
-                       R, ldr, Y, ldy, rows, ncols, K, C, ntm, ntn);
-  } else {
-    ensure_smem(gemm_x6_kernel<NW, TN, false>, smem);
-    hipLaunchKernelGGL((gemm_x6_kernel<NW, TN, false>), dim3(ntm * ntn), dim3(NW * 64), smem, s, X, ldx, Wp, ldp,
-                       bias, R, ldr, Y, ldy, rows, ncols, K, C, ntm, ntn);
-  }
-}
-
-// ---- big-tile form: 256 x (64*TN) tiles, 4 x 2 waves of 64 x 32*TN, BK = 16, DMA ring ----
-// Intensity: per 16-k step a workgroup moves 256 x 64 B of A (f32) + BN x 96 B of B (three
-// planes) for 2 x 256 x BN x 16 flops: 51 flop/B at BN = 256 (the 64-row tiles above move
-// 2x the bytes per flop, which the L2 -> CU path cannot feed at bf16 MFMA rate).
-// LDS images per stage: A [256][64 B], 16-B slot s of row m at s ^ ((m >> 2) & 3);
-// B [plane][BN][32 B], slot h of row n at h ^ ((n >> 3) & 1)  (conflict-free b128 reads).
-// Every wave issues exactly PER DMA instructions per stage (surplus slots repeat the last
-// piece, an identical write), so the counted vmcnt waits are exact.
-template <int TN, int STAGES>
-__global__ __launch_bounds__(512) void gemm_x6b_kernel(const float* __restrict__ X, int ldx,
-                                                       const uint16_t* __restrict__ Wp, int ldp,
-                                                       const float* __restrict__ bias, const float* R, int ldr,
-                                                       float* Y, int ldy, int rows, int ncols, int K, int C, int ntm,
-                                                       int ntn) {
-  constexpr int NW = 8, BM = 256, WN = 32 * TN, BN = 2 * WN, BK = 16;
-  constexpr int A_BYTES = BM * BK * 4, B_PLANE = BN * BK * 2, STAGE = A_BYTES + 3 * B_PLANE;
-  constexpr int IA = A_BYTES / 1024, IB = 3 * B_PLANE / 1024, PER = (IA + IB + NW - 1) / NW;
-  static_assert(A_BYTES % 1024 == 0 && B_PLANE % 1024 == 0, "DMA pieces");
-  extern __shared__ float4 smem4[];
-  char* smem = reinterpret_cast<char*>(smem4);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid >> 1, wn = wid & 1;
-  const int l32 = lane & 31, lh = lane >> 5;
-
-  const int nblk = ntm * ntn;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk / 8, r8 = nblk % 8, xcd = bid % 8, slot = bid / 8;
-    bid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + slot;
-  }
-  const int tm = bid / ntn, tn = bid % ntn;
-  const int row0 = tm * BM, col0 = tn * BN;
-  const size_t plane = (size_t)ldp * K;
-  const uint32_t lds0 = (uint32_t)(size_t)((__attribute__((address_space(3))) char*)smem);
-
-  auto stage = [&](int k0, int buf) {
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-      int j = wid + t * NW;
-      if (j >= IA + IB) j = IA + IB - 1;  // wave-uniform: repeat the last piece
-      const void* src;
-      uint32_t dst;
-      if (j < IA) {  // 16 rows x 64 B of f32 activations
-        const int r = j * 16 + (lane >> 2);
-        const int sl = ((lane & 3) ^ ((r >> 2) & 3)) * 4;
-        src = X + (size_t)(row0 + r) * ldx + k0 + sl;
-        dst = lds0 + (uint32_t)(buf * STAGE + j * 1024);
-      } else {  // 32 rows x 32 B of one weight plane
-        const int jb = j - IA, p = jb / (B_PLANE / 1024), rg = (jb % (B_PLANE / 1024)) * 32;
-        const int r = rg + (lane >> 1);
-        const int sl = ((lane & 1) ^ ((r >> 3) & 1)) * 8;
-        src = Wp + p * plane + (size_t)(col0 + r) * K + k0 + sl;
-        dst = lds0 + (uint32_t)(buf * STAGE + A_BYTES + p * B_PLANE + rg * 32);
-      }
-      dst = __builtin_amdgcn_readfirstlane(dst);
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep)
-                   : "v"(src), "s"(dst)
-                   : "memory");
-    }
-  };
-
-  f32x16 acc[2][TN];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  const int nk = K / BK;
-#pragma unroll
-  for (int t = 0; t < STAGES - 1; ++t)
-    if (t < nk) stage(t * BK, t);
-  int cur = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    if (STAGES == 3 && kt + 1 < nk)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(PER) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kt + STAGES - 1 < nk) {
-      int nb = cur + STAGES - 1;
-      if (nb >= STAGES) nb -= STAGES;
-      stage((kt + STAGES - 1) * BK, nb);
-    }
-    const char* As = smem + cur * STAGE;
-    const char* Bs = As + A_BYTES;
-    if (++cur == STAGES) cur = 0;
-    bf16x8 a0[2], a1[2], a2[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {  // A fragment: row m, k = 8 lh + (0..7) = slots 2lh, 2lh+1
-      const int m = wm * 64 + i * 32 + l32;
-      const float* arow = reinterpret_cast<const float*>(As) + m * BK;
-      const float4 u = *reinterpret_cast<const float4*>(arow + (((2 * lh) ^ ((m >> 2) & 3)) * 4));
-      const float4 v = *reinterpret_cast<const float4*>(arow + (((2 * lh + 1) ^ ((m >> 2) & 3)) * 4));
-      split3(u, v, a0[i], a1[i], a2[i]);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int n = wn * WN + j * 32 + l32;
-      const int off = n * 32 + ((lh ^ ((n >> 3) & 1)) * 16);
-      const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(Bs + off);
-      const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(Bs + B_PLANE + off);
-      const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(Bs + 2 * B_PLANE + off);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[i], b0, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[i], b2, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[i], b1, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[i], b0, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[i], b1, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[i], b0, acc[i][j], 0, 0, 0);
-      }
-    }
-  }
-
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int rbase = row0 + wm * 64 + i * 32 + 4 * lh;
-    const int rm0 = (C == 1) ? 0 : rbase % C;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int c = col0 + wn * WN + j * 32 + l32;
-      if (c >= ncols) continue;
-      const float bv = bias ? bias[c] : 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int off = (e & 3) + 8 * (e >> 2);
-        const int r = rbase + off;
-        if (r >= rows) continue;
-        float v = acc[i][j][e];
-        if (bias) {
-          int t = rm0 + off;
-          while (t >= C) t -= C;
-          if (t == 0) v += bv;
-        }
-        if (R) v += R[(size_t)r * ldr + c];
-        Y[(size_t)r * ldy + c] = v;
-      }
-    }
-  }
-}
-
-template <int TN, int STAGES>
-void launch_x6b_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
-                  float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
-  constexpr int BM = 256, BN = 64 * TN;
-  const int ntm = (rows + BM - 1) / BM, ntn = (ncols + BN - 1) / BN;
-  const size_t smem = (size_t)STAGES * (BM * 16 * 4 + 3 * BN * 16 * 2);
-  ensure_smem(gemm_x6b_kernel<TN, STAGES>, smem);
-  hipLaunchKernelGGL((gemm_x6b_kernel<TN, STAGES>), dim3(ntm * ntn), dim3(512), smem, s, X, ldx, Wp, ldp, bias, R,
-                     ldr, Y, ldy, rows, ncols, K, C, ntm, ntn);
-}
-
-// ---- pipelined form: 256 x 32*TN tiles, 8 waves of 32 x 32*TN, BK = 16, 3-buffer ring ----
-// The split of the NEXT k-tile's activations runs between the MFMAs of the current one
-// (its f32 fragment is read from LDS one k-tile ahead), so the matrix cores do not idle
-// through a VALU-only phase after every barrier.  Ring: at iteration kt the DMA fills
-// buffer (kt+2)%3 (last read in iteration kt-1, retired by this iteration's barrier), A of
-// kt+1 is read from buffer (kt+1)%3 (landed: vmcnt(0) + barrier), B of kt from kt%3.
-// Every activation element is split by exactly one wave (wave w owns rows 32w..32w+31).
-template <int TN>
-__global__ __launch_bounds__(512) void gemm_x6c_kernel(const float* __restrict__ X, int ldx,
-                                                       const uint16_t* __restrict__ Wp, int ldp,
-                                                       const float* __restrict__ bias, const float* R, int ldr,
-                                                       float* Y, int ldy, int rows, int ncols, int K, int C, int ntm,
-                                                       int ntn) {
-  constexpr int NW = 8, BM = 256, BN = 32 * TN, BK = 16;
-  constexpr int A_BYTES = BM * BK * 4, B_PLANE = BN * BK * 2, STAGE = A_BYTES + 3 * B_PLANE;
-  constexpr int IA = A_BYTES / 1024, IB = (3 * B_PLANE + 1023) / 1024, PER = (IA + IB + NW - 1) / NW;
-  static_assert(A_BYTES % 1024 == 0 && (3 * B_PLANE) % 1024 == 0, "DMA pieces");
-  extern __shared__ float4 smem4[];
-  char* smem = reinterpret_cast<char*>(smem4);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l32 = lane & 31, lh = lane >> 5;
-
-  const int nblk = ntm * ntn;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk / 8, r8 = nblk % 8, xcd = bid % 8, slot = bid / 8;
-    bid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + slot;
-  }
-  const int tm = bid / ntn, tn = bid % ntn;
-  const int row0 = tm * BM, col0 = tn * BN;
-  const size_t plane = (size_t)ldp * K;
-  const uint32_t lds0 = (uint32_t)(size_t)((__attribute__((address_space(3))) char*)smem);
-
-  auto stage = [&](int k0, int buf) {
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-      int j = wid + t * NW;
-      if (j >= IA + IB) j = IA + IB - 1;  // wave-uniform: repeat the last piece
-      const void* src;
-      uint32_t dst;
-      if (j < IA) {  // 16 rows x 64 B of f32 activations
-        const int r = j * 16 + (lane >> 2);
-        const int sl = ((lane & 3) ^ ((r >> 2) & 3)) * 4;
-        src = X + (size_t)(row0 + r) * ldx + k0 + sl;
-        dst = lds0 + (uint32_t)(buf * STAGE + j * 1024);
-      } else {  // 32 rows x 32 B of the weight planes, rows (plane, n) contiguous
-        const int q = (j - IA) * 32 + (lane >> 1);  // global row of the [3][BN] image
-        const int p = q / BN, n = q % BN;
-        const int sl = ((lane & 1) ^ ((n >> 3) & 1)) * 8;
-        src = Wp + p * plane + (size_t)(col0 + n) * K + k0 + sl;
-        dst = lds0 + (uint32_t)(buf * STAGE + A_BYTES + (j - IA) * 1024);
-      }
-      dst = __builtin_amdgcn_readfirstlane(dst);
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep)
-                   : "v"(src), "s"(dst)
-                   : "memory");
-    }
-  };
-  const int m = wid * 32 + l32;  // this lane's A row within the tile
-  auto read_a = [&](int buf, float4& u, float4& v) {
-    const float* arow = reinterpret_cast<const float*>(smem + buf * STAGE) + m * BK;
-    u = *reinterpret_cast<const float4*>(arow + (((2 * lh) ^ ((m >> 2) & 3)) * 4));
-    v = *reinterpret_cast<const float4*>(arow + (((2 * lh + 1) ^ ((m >> 2) & 3)) * 4));
-  };
-
-  f32x16 acc[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-
-  const int nk = K / BK;
-  stage(0, 0);
-  if (nk > 1) stage(BK, 1);
-  if (nk > 1)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(PER) : "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  bf16x8 c0, c1, c2;  // split fragments of the current k-tile
-  {
-    float4 u, v;
-    read_a(0, u, v);
-    split3(u, v, c0, c1, c2);
-  }
-  int bcur = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stage kt+1 (issued one iteration ago)
-    __syncthreads();
-    int bn1 = bcur + 1, bn2 = bcur + 2;
-    if (bn1 >= 3) bn1 -= 3;
-    if (bn2 >= 3) bn2 -= 3;
-    if (kt + 2 < nk) stage((kt + 2) * BK, bn2);
-    const bool more = kt + 1 < nk;
-    float4 u, v;
-    if (more) read_a(bn1, u, v);
-    const char* Bs = smem + bcur * STAGE + A_BYTES;
-    bf16x8 n0, n1, n2;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int n = j * 32 + l32;
-      const int off = n * 32 + ((lh ^ ((n >> 3) & 1)) * 16);
-      const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(Bs + off);
-      const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(Bs + B_PLANE + off);
-      const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(Bs + 2 * B_PLANE + off);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c2, b0, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c0, b2, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c1, b1, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c1, b0, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c0, b1, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c0, b0, acc[j], 0, 0, 0);
-      if (j == TN / 2 && more) split3(u, v, n0, n1, n2);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    if (more) {
-      c0 = n0;
-      c1 = n1;
-      c2 = n2;
-    }
-    bcur = bn1;
-  }
-
-  const int rbase = row0 + wid * 32 + 4 * lh;
-  const int rm0 = (C == 1) ? 0 : rbase % C;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int c = col0 + j * 32 + l32;
-    if (c >= ncols) continue;
-    const float bv = bias ? bias[c] : 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int off = (e & 3) + 8 * (e >> 2);
-      const int r = rbase + off;
-      if (r >= rows) continue;
-      float val = acc[j][e];
-      if (bias) {
-        int t = rm0 + off;
-        while (t >= C) t -= C;
-        if (t == 0) val += bv;
-      }
-      if (R) val += R[(size_t)r * ldr + c];
-      Y[(size_t)r * ldy + c] = val;
-    }
-  }
-}
-
-template <int TN>
-void launch_x6c_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
-                  float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
-  constexpr int BM = 256, BN = 32 * TN;
-  const int ntm = (rows + BM - 1) / BM, ntn = (ncols + BN - 1) / BN;
-  const size_t smem = 3ull * (BM * 16 * 4 + 3 * BN * 16 * 2);
-  ensure_smem(gemm_x6c_kernel<TN>, smem);
-  hipLaunchKernelGGL((gemm_x6c_kernel<TN>), dim3(ntm * ntn), dim3(512), smem, s, X, ldx, Wp, ldp, bias, R, ldr, Y,
-                     ldy, rows, ncols, K, C, ntm, ntn);
-}
-
 // ---- lean pipelined form (the production kernel) -------------------------------------------
-// As gemm_x6c_kernel (256 x 32*TN tiles, 8 waves of 32 rows, BK = 16, 3-buffer ring, next
-// k-tile's split between the current MFMAs), with the issue budget of a bf16 MFMA in mind
+// 32 NW x 32*TN*WN tiles, BK = 16, a ring of ST DMA buffers; wave w owns rows 32w..32w+31, so
+// every activation element is split exactly once, and the split of the NEXT k-tile's
+// activations runs between the MFMAs of the current one (its f32 fragment is read from LDS
+// one k-tile ahead), so the matrix cores do not idle through a VALU-only phase after every
+// barrier.  Written with the issue budget of a bf16 MFMA in mind
 // (an MFMA gap of 32 cycles holds ~6 VALU issues, MI355X_MICROARCH.md cycle table):
 //  * DMA sources are a per-lane 32-bit offset fixed for the whole tile plus a scalar base
 //    advanced per k-tile (global_load_lds saddr form: no VALU address math in the loop);
@@ -655,8 +157,6 @@ void launch_x6c_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const fl
 //    l32 only), A fragment addresses lane-constant + the buffer base;
 //  * interior tiles store without row / column guards; the channel-bias rows of a lane's 32
 //    rows are a bit mask computed once per tile.
-// ABL (ablation, tools only): 0 full; 1 no DMA / barriers (LDS contents stale); 2 also no
-// split (fragments reinterpreted); 3 also no LDS reads (MFMAs on register operands only).
 // NW waves (BM = 32 NW).  ST = 3: the ring above (one workgroup per CU at NW = 8).  ST = 2:
 // two buffers, the k-tile's own split at its top and one barrier per k-tile; at NW = 4,
 // TN = 8 a workgroup takes 64 KiB of LDS, so two share a CU and one's epilogue stores
@@ -669,7 +169,7 @@ void launch_x6c_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const fl
 // its 32 x 256 block into LDS once, then sweeps it three times (pre-LN value + mean,
 // centred variance, normalise + store) with 16 lanes per row.  X (= h in LNM 2) is only
 // read by the DMA of this workgroup's own rows, all landed before the epilogue barrier.
-template <int TN, int ABL = 0, int NW = 8, int ST = 3, int LNM = 0, int WN = 1>
+template <int TN, int NW = 8, int ST = 3, int LNM = 0, int WN = 1>
 __global__ __launch_bounds__(NW * WN * 64) __attribute__((amdgpu_waves_per_eu(NW * WN >= 8 ? 1 : 8 / (NW * WN)))) void gemm_x6d_kernel(const float* X, int ldx,
                                                        const uint16_t* __restrict__ Wp, int ldp,
                                                        const float* __restrict__ bias, const float* R, int ldr,
@@ -677,16 +177,13 @@ __global__ __launch_bounds__(NW * WN * 64) __attribute__((amdgpu_waves_per_eu(NW
                                                        int ntn, const float* __restrict__ ln, X6Feat feat) {
   // NW x WN waves: wave (wm, wn) computes rows 32 wm.. and columns 32 TN wn.. of the tile
   constexpr int NWT = NW * WN;
-  // ablation switches (ABL 5: the full main loop, no epilogue)
-  constexpr bool A_DMA = ABL == 0 || ABL >= 5, A_SPLIT = ABL < 2 || ABL >= 5, A_LDS = ABL < 3 || ABL >= 5;
   constexpr int BM = 32 * NW, BN = 32 * TN * WN, BK = 16;
   static_assert(LNM == 0 || BN == 256, "LayerNorm epilogue needs whole 256-column rows");
   static_assert(WN == 1 || BN == 256, "shared-tile epilogue: 64 lanes x 4 columns");
   constexpr int A_BYTES = BM * BK * 4, B_PLANE = BN * BK * 2, STAGE = A_BYTES + 3 * B_PLANE;
   constexpr int IA = A_BYTES / 1024, IB = (3 * B_PLANE) / 1024, PER = (IA + IB + NWT - 1) / NWT;
   static_assert(A_BYTES % 1024 == 0 && (3 * B_PLANE) % 1024 == 0, "DMA pieces");
-  static_assert(ST >= 2 && ST <= 6, "ring depth");
-  static_assert(ST <= 3 || (ST - 3) * PER <= 63, "vmcnt range");
+  static_assert(ST == 2 || ST == 3, "ring depth");
   extern __shared__ float4 smem4[];
   char* smem = reinterpret_cast<char*>(smem4);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -787,10 +284,10 @@ __global__ __launch_bounds__(NW * WN * 64) __attribute__((amdgpu_waves_per_eu(NW
       __syncthreads();                                  // ... and buffer cur is free
     }
   } else {
-  // ring of ST buffers, ST - 2 stages in flight while a k-tile computes: stages 0 .. ST-2
-  // issued up front; at k-tile kt, wait for stage kt + 1 (the younger ST - 3 may stay in
-  // flight: VMEM ops of a wave complete in order), barrier, issue stage kt + ST - 1 into the
-  // buffer k-tile kt - 1 used
+  // ring of three buffers, one stage in flight while a k-tile computes: stages 0, 1 issued up
+  // front; at k-tile kt, wait for stage kt + 1, barrier, issue stage kt + 2 into the buffer
+  // k-tile kt - 1 used.  (Deeper rings, two or three stages in flight, were no faster:
+  // profiles/r02_ring_depth_bench.json.)
   for (int t = 0; t < ST - 1 && t < nk; ++t) stage(t, t);
   if (nk > ST - 2)
     asm volatile("s_waitcnt vmcnt(%0)" ::"i"((ST - 2) * PER) : "memory");
@@ -804,77 +301,26 @@ __global__ __launch_bounds__(NW * WN * 64) __attribute__((amdgpu_waves_per_eu(NW
     split3(u, v, c0, c1, c2);
   }
   int bcur = 0;
-  bf16x8 rb0 = c0, rb1 = c1, rb2 = c2;  // ABL 3 operands
-  constexpr bool PB = A_LDS && A_SPLIT;  // B reads pipelined one column block ahead
-  bf16x8 nb[3];
-  if constexpr (PB) {
-    nb[0] = *reinterpret_cast<const bf16x8*>(smem + boff);
-    nb[1] = *reinterpret_cast<const bf16x8*>(smem + boff + B_PLANE);
-    nb[2] = *reinterpret_cast<const bf16x8*>(smem + boff + 2 * B_PLANE);
-  }
+  bf16x8 nb[3];  // B reads pipelined one column block ahead: block 0 of the current k-tile
+  nb[0] = *reinterpret_cast<const bf16x8*>(smem + boff);
+  nb[1] = *reinterpret_cast<const bf16x8*>(smem + boff + B_PLANE);
+  nb[2] = *reinterpret_cast<const bf16x8*>(smem + boff + 2 * B_PLANE);
   for (int kt = 0; kt < nk; ++kt) {
-    if (A_DMA) {
-      if (ST > 3 && kt + ST - 2 < nk)  // stages kt + 2 .. kt + ST - 2 issued: they may stay in flight
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"((ST > 3 ? ST - 3 : 0) * PER) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stage kt+1 (issued earlier)
-      __syncthreads();
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stage kt+1 (issued earlier)
+    __syncthreads();
     int bn1 = bcur + 1, bnl = bcur + ST - 1;
     if (bn1 >= ST) bn1 -= ST;
     if (bnl >= ST) bnl -= ST;
-    if (A_DMA && kt + ST - 1 < nk) stage(kt + ST - 1, bnl);
+    if (kt + ST - 1 < nk) stage(kt + ST - 1, bnl);
     const bool more = kt + 1 < nk;
-    float4 u, v;
-    if (PB) {  // the next stage's A (stale past the last k-tile: split but never used)
-      const char* An = smem + bn1 * STAGE;
-      u = *reinterpret_cast<const float4*>(An + aoff0);
-      v = *reinterpret_cast<const float4*>(An + aoff1);
-    } else if (more) {
-      if (A_LDS) {
-        const char* An = smem + bn1 * STAGE;  // ABL 3, 4: no LDS reads
-        u = *reinterpret_cast<const float4*>(An + aoff0);
-        v = *reinterpret_cast<const float4*>(An + aoff1);
-      } else {
-        u = make_float4(kt, 1.f, 2.f, 3.f);
-        v = u;
-      }
-    }
+    // the next stage's A (stale past the last k-tile: split but never used)
+    const char* An = smem + bn1 * STAGE;
+    const float4 u = *reinterpret_cast<const float4*>(An + aoff0);
+    const float4 v = *reinterpret_cast<const float4*>(An + aoff1);
     const char* Bs = smem + bcur * STAGE + boff;
     bf16x8 n0, n1, n2;
     __builtin_amdgcn_s_setprio(1);
-    if constexpr (PB) {
-      ktile_pipelined<TN, B_PLANE>(Bs, smem + bn1 * STAGE + boff, acc, nb, c0, c1, c2, u, v, n0, n1, n2);
-    } else {
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      bf16x8 b0, b1, b2;
-      if (A_LDS) {
-        b0 = *reinterpret_cast<const bf16x8*>(Bs + j * 1024);
-        b1 = *reinterpret_cast<const bf16x8*>(Bs + B_PLANE + j * 1024);
-        b2 = *reinterpret_cast<const bf16x8*>(Bs + 2 * B_PLANE + j * 1024);
-      } else {
-        b0 = rb0;
-        b1 = rb1;
-        b2 = rb2;
-      }
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, c2, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b2, c0, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, c1, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, c1, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, c0, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, c0, acc[j], 0, 0, 0);
-      if (j == TN / 2 && more) {
-        if (A_SPLIT) {
-          split3(u, v, n0, n1, n2);
-        } else {
-          n0 = __builtin_bit_cast(bf16x8, u);
-          n1 = __builtin_bit_cast(bf16x8, v);
-          n2 = n0;
-        }
-      }
-    }
-    }
+    ktile_pipelined<TN, B_PLANE>(Bs, smem + bn1 * STAGE + boff, acc, nb, c0, c1, c2, u, v, n0, n1, n2);
     __builtin_amdgcn_s_setprio(0);
     if (more) {
       c0 = n0;
@@ -885,15 +331,6 @@ __global__ __launch_bounds__(NW * WN * 64) __attribute__((amdgpu_waves_per_eu(NW
   }
   }  // ST == 3
 
-  if (ABL == 4 || ABL == 5) {  // ablation: no stores unless the impossible happens (keeps the MFMAs live)
-    float t = 0.f;
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) t += acc[j][e];
-    if (t == 1234.5f) Y[tid] = t;
-    return;
-  }
   // epilogue.  The MFMA operands are swapped (weight fragment as A), so register e of
   // acc[j] holds output row rw0 + l32, column 32j + 8(e >> 2) + 4lh + (e & 3): four
   // consecutive columns per register group.  Each wave transposes 32 x 64-column panels
@@ -973,7 +410,7 @@ __global__ __launch_bounds__(NW * WN * 64) __attribute__((amdgpu_waves_per_eu(NW
           t.y += bv[k].y;
           t.z += bv[k].z;
           t.w += bv[k].w;
-          if (LNM == 2 && ABL != 7) {  // ABL 7: ablation, no tanh
+          if (LNM == 2) {
             t.x = tanh_rat(t.x);
             t.y = tanh_rat(t.y);
             t.z = tanh_rat(t.z);
@@ -1000,7 +437,7 @@ __global__ __launch_bounds__(NW * WN * 64) __attribute__((amdgpu_waves_per_eu(NW
           v[k] = t;
           sum += (t.x + t.y) + (t.z + t.w);
         }
-        const float mean = (ABL == 6 ? sum : row16_sum(sum)) * (1.f / 256.f);
+        const float mean = row16_sum(sum) * (1.f / 256.f);
         float ss = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -1010,7 +447,7 @@ __global__ __launch_bounds__(NW * WN * 64) __attribute__((amdgpu_waves_per_eu(NW
           v[k].w -= mean;
           ss += (v[k].x * v[k].x + v[k].y * v[k].y) + (v[k].z * v[k].z + v[k].w * v[k].w);
         }
-        const float var = (ABL == 6 ? ss : row16_sum(ss)) * (1.f / 256.f);
+        const float var = row16_sum(ss) * (1.f / 256.f);
         const float rs = __builtin_amdgcn_rsqf(var + 1e-5f);
         if (r < rows) {
 #pragma unroll
@@ -1130,7 +567,7 @@ __global__ __launch_bounds__(NW * WN * 64) __attribute__((amdgpu_waves_per_eu(NW
   }
 }
 
-template <int TN, int ABL = 0, int NW = 8, int ST = 3, int LNM = 0, int WN = 1>
+template <int TN, int NW = 8, int ST = 3, int LNM = 0, int WN = 1>
 void launch_x6d_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
                   float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s, const float* ln = nullptr,
                   X6Feat feat = X6Feat{}) {
@@ -1140,8 +577,8 @@ void launch_x6d_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const fl
   // (a shared BM x 260-float tile of whole rows with the LayerNorm epilogue or WN > 1)
   const size_t smem =
       std::max((size_t)ST * (BM * 16 * 4 + 3 * BN * 16 * 2), (size_t)(LNM || WN > 1 ? BM * 260 : NW * 32 * 68) * 4);
-  ensure_smem(gemm_x6d_kernel<TN, ABL, NW, ST, LNM, WN>, smem);
-  hipLaunchKernelGGL((gemm_x6d_kernel<TN, ABL, NW, ST, LNM, WN>), dim3(ntm * ntn), dim3(NW * WN * 64), smem, s, X,
+  ensure_smem(gemm_x6d_kernel<TN, NW, ST, LNM, WN>, smem);
+  hipLaunchKernelGGL((gemm_x6d_kernel<TN, NW, ST, LNM, WN>), dim3(ntm * ntn), dim3(NW * WN * 64), smem, s, X,
                      ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, ntm, ntn, ln, feat);
 }
 
@@ -1152,11 +589,10 @@ void launch_x6d_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const fl
 // transposes through its own LDS region (not the ring) and its 4*TN dwordx4 stores stay
 // in flight under the next steps (counted: vmcnt(4*TN) at the next step's wait; VMEM ops of
 // a wave complete in order).  LDS: ring 3 x 40 KiB + 8 x 4.5 KiB transpose = 156 KiB.
-// R4: a 4-stage ring (160 KiB, two stages in flight instead of one: the DMA latency cover
-// doubles).  No LDS is left for a transpose region, so a tile's last step does not issue
-// its step + 3 DMA: the epilogue transposes through that free stage buffer, and the next
-// step issues two stages (its wait then counts the epilogue's stores instead).
-template <int TN, bool HAS_R, bool R4 = false, int ABLQ = 0, bool PB = false>  // ABLQ 1: no epilogue stores (tools only)
+// PB: the B fragment reads pipelined one column block ahead (ktile_pipelined).
+// (A 4-stage ring, two DMA stages in flight, was slower: el_qkv 954 -> 976 us,
+// profiles/r02_gemm_ablations.txt: DMA latency is not what limits it.)
+template <int TN, bool HAS_R, bool PB = false>
 __global__ __launch_bounds__(512) void gemm_x6q_kernel(const float* __restrict__ X, int ldx,
                                                        const uint16_t* __restrict__ Wp, int ldp,
                                                        const float* __restrict__ bias, const float* R, int ldr,
@@ -1168,7 +604,7 @@ __global__ __launch_bounds__(512) void gemm_x6q_kernel(const float* __restrict__
   constexpr int NST = 4 * TN, TS = 36;  // stores per wave per tile; transpose row stride (floats)
   static_assert(A_BYTES % 1024 == 0 && (3 * B_PLANE) % 1024 == 0, "DMA pieces");
   static_assert(PER + NST <= 63, "vmcnt range");
-  constexpr int NS = R4 ? 4 : 3;  // ring stages
+  constexpr int NS = 3;  // ring stages
   extern __shared__ float4 smem4[];
   char* smem = reinterpret_cast<char*>(smem4);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1228,7 +664,7 @@ __global__ __launch_bounds__(512) void gemm_x6q_kernel(const float* __restrict__
   const int aoff0 = m * 64 + (((2 * lh) ^ ((m >> 2) & 3)) * 16);
   const int aoff1 = m * 64 + (((2 * lh + 1) ^ ((m >> 2) & 3)) * 16);
   const int boff = A_BYTES + l32 * 32 + ((lh ^ ((l32 >> 3) & 1)) * 16);
-  float* red = reinterpret_cast<float*>(smem + 3 * STAGE) + wid * (32 * TS);  // R4: set per tile
+  float* red = reinterpret_cast<float*>(smem + 3 * STAGE) + wid * (32 * TS);
   const int lr = lane >> 3, lc = (lane & 7) * 4;  // read-back: rows 8q + lr, columns lc..lc+3
 
   f32x16 acc[TN];
@@ -1239,10 +675,7 @@ __global__ __launch_bounds__(512) void gemm_x6q_kernel(const float* __restrict__
 
   stage(0, 0);
   if (F > 1) stage(1, 1);
-  if (R4 && F > 2) stage(2, 2);
-  if (R4 && F > 2)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * PER) : "memory");
-  else if (F > 1)
+  if (F > 1)
     asm volatile("s_waitcnt vmcnt(%0)" ::"i"(PER) : "memory");
   else
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1261,42 +694,23 @@ __global__ __launch_bounds__(512) void gemm_x6q_kernel(const float* __restrict__
   }
   int bcur = 0, kt = 0, tile = 0;
   bool stored = false;  // epilogue stores issued in the previous step
-  bool deferred = false;  // R4: the previous (tile-end) step left its step + 3 DMA to this one
   for (int f = 0; f < F; ++f) {
-    // wait for step f+1's DMA; younger: (ST 3) the previous epilogue's stores, (R4) step
-    // f+2's DMA, or, after a tile end, the epilogue's stores
-    if constexpr (R4) {
-      if (deferred && stored)  // exactly NST stores behind step f+1's DMA
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NST) : "memory");
-      else if (deferred)  // a partial tile's guarded stores: drain
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if (f + 2 < F)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(PER) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      if (stored)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NST) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    // wait for step f+1's DMA; younger: the previous epilogue's stores
+    if (stored)
+      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NST) : "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     stored = false;
-    int bn1 = bcur + 1, bn2 = bcur + 2, bn3 = bcur + 3;
+    int bn1 = bcur + 1, bn2 = bcur + 2;
     if (bn1 >= NS) bn1 -= NS;
     if (bn2 >= NS) bn2 -= NS;
-    if (bn3 >= NS) bn3 -= NS;
-    const bool tile_end = kt + 1 == nk;
-    if constexpr (R4) {
-      if (deferred && f + 2 < F) stage(f + 2, bn2);  // the transpose buffer of the last epilogue
-      if (!tile_end && f + 3 < F) stage(f + 3, bn3);  // the buffer step f-1 read
-      deferred = tile_end;
-      if (tile_end) red = reinterpret_cast<float*>(smem + bn3 * STAGE) + wid * (32 * TS);
-    } else {
-      if (f + 2 < F) stage(f + 2, bn2);
-    }
+    // (kt + 1 is formed here, not at its use below, only so that the compiler keeps the instruction
+    // order of the kernel that was measured: profiles/gemm_prune_isa.txt compares the two)
+    const int kt_next = kt + 1;
+    if (f + 2 < F) stage(f + 2, bn2);
     const bool more = f + 1 < F;
     float4 u, v;
     if (PB) {  // the next stage's A (stale past the last k-tile: split but never used)
@@ -1335,7 +749,8 @@ __global__ __launch_bounds__(512) void gemm_x6q_kernel(const float* __restrict__
       c2 = n2;
     }
     bcur = bn1;
-    if (++kt < nk) continue;
+    kt = kt_next;
+    if (kt < nk) continue;
     // ---- tile done: epilogue (MFMA layout: acc[j] reg e = row rw0 + l32, column
     // 32j + 8(e>>2) + 4lh + (e&3)); transpose 32 x 32 blocks through `red`, dwordx4 stores
     int row0, col0;
@@ -1400,8 +815,7 @@ __global__ __launch_bounds__(512) void gemm_x6q_kernel(const float* __restrict__
             val.z += rcur[q].z;
             val.w += rcur[q].w;
           }
-          if (ABLQ == 0 || val.x == 1.2345e-30f)
-            *reinterpret_cast<float4*>(Y + (size_t)(rw0 + rr) * ldy + col0 + 32 * j + lc) = val;
+          *reinterpret_cast<float4*>(Y + (size_t)(rw0 + rr) * ldy + col0 + 32 * j + lc) = val;
         }
         if (HAS_R) {
 #pragma unroll
@@ -1433,172 +847,28 @@ __global__ __launch_bounds__(512) void gemm_x6q_kernel(const float* __restrict__
     }
     // full tiles issue exactly NST stores per wave (the count the next wait assumes);
     // partial tiles drain everything at the next wait
-    stored = full && ABLQ == 0;
+    stored = full;
   }
 }
 
-template <int TN, bool R4 = false, int ABLQ = 0, bool PB = false>
+template <int TN, bool PB = false>
 void launch_x6q_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
                   float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
   constexpr int BM = 256, BN = 32 * TN;
   const int ntm = (rows + BM - 1) / BM, ntn = (ncols + BN - 1) / BN;
   const size_t st = BM * 16 * 4 + 3 * BN * 16 * 2;
-  const size_t smem = R4 ? 4ull * st : 3ull * st + 8ull * 32 * 36 * 4;
-  static_assert(!R4 || BM * 16 * 4 + 3 * BN * 16 * 2 >= 8 * 32 * 36 * 4, "transpose fits a stage");
+  const size_t smem = 3ull * st + 8ull * 32 * 36 * 4;
   int grid = std::min(ntm * ntn, cu_count_x6());
   grid = std::max(8, grid / 8 * 8);
   if (R) {
-    ensure_smem(gemm_x6q_kernel<TN, true, R4, ABLQ, PB>, smem);
-    hipLaunchKernelGGL((gemm_x6q_kernel<TN, true, R4, ABLQ, PB>), dim3(grid), dim3(512), smem, s, X, ldx, Wp, ldp, bias, R,
+    ensure_smem(gemm_x6q_kernel<TN, true, PB>, smem);
+    hipLaunchKernelGGL((gemm_x6q_kernel<TN, true, PB>), dim3(grid), dim3(512), smem, s, X, ldx, Wp, ldp, bias, R,
                        ldr, Y, ldy, rows, ncols, K, C, ntm, ntn);
   } else {
-    ensure_smem(gemm_x6q_kernel<TN, false, R4, ABLQ, PB>, smem);
-    hipLaunchKernelGGL((gemm_x6q_kernel<TN, false, R4, ABLQ, PB>), dim3(grid), dim3(512), smem, s, X, ldx, Wp, ldp, bias,
+    ensure_smem(gemm_x6q_kernel<TN, false, PB>, smem);
+    hipLaunchKernelGGL((gemm_x6q_kernel<TN, false, PB>), dim3(grid), dim3(512), smem, s, X, ldx, Wp, ldp, bias,
                        R, ldr, Y, ldy, rows, ncols, K, C, ntm, ntn);
   }
-}
-
-// ---- persistent form: weight panel resident in LDS, activations straight to registers ----
-// A workgroup owns one 64-column panel of the output for its whole life: the three bf16
-// planes of that weight panel (64 x K x 3 x 2 B = 96 KiB at K = 256) are loaded into LDS
-// once, then every wave walks its own 32-row tiles with NO barrier: it loads its A rows
-// from global memory straight into registers (lane (r, h) holds row r, k = 32t + 16h ..
-// +15 of k-tile t: 64 contiguous bytes, the two lane halves covering a 128-B line), one
-// k-tile ahead, splits them and runs 2 x 6 MFMAs per 16-k chunk against B fragments read
-// from LDS.  B k labelling matches: chunk c of k-tile t takes k = 32t + 16h + 8c + j.
-// LDS image: [plane][64 rows][K] bf16, 16-B slot s of row n stored at s ^ (n & 15).
-// Groups of P workgroups (one per panel, adjacent logical ids, i.e. one XCD) walk the
-// same row tiles, so each A row is fetched from HBM once and re-read from L2.
-constexpr int XP_BN = 64;
-
-template <int NW, bool HAS_R>
-__global__ __launch_bounds__(NW * 64) void gemm_x6p_kernel(const float* __restrict__ X, int ldx,
-                                                           const uint16_t* __restrict__ Wp, int ldp,
-                                                           const float* __restrict__ bias, const float* R, int ldr,
-                                                           float* Y, int ldy, int rows, int ncols, int K, int C,
-                                                           int P, int ngroups) {
-  extern __shared__ float4 smem4[];
-  char* smem = reinterpret_cast<char*>(smem4);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l32 = lane & 31, lh = lane >> 5;
-  // logical id: consecutive ids share an XCD (gridDim.x is a multiple of 8)
-  const int g = blockIdx.x, per_xcd = gridDim.x / 8;
-  const int L = (g % 8) * per_xcd + g / 8;
-  const int group = L / P, panel = L % P;
-  if (group >= ngroups) return;  // whole workgroup exits (no barrier reached)
-  const int col0 = panel * XP_BN;
-  const int row_bytes = K * 2, slots = K / 8;  // one B row: K bf16 = K/8 slots of 16 B
-  const int plane_bytes = XP_BN * row_bytes;
-  // ---- load the weight panel (three planes) into LDS, swizzled
-  {
-    const int total = 3 * XP_BN * slots;  // 16-B pieces
-    for (int q = tid; q < total; q += NW * 64) {
-      const int p = q / (XP_BN * slots), rem = q % (XP_BN * slots);
-      const int n = rem / slots, s = rem % slots;
-      const uint4 v =
-          *reinterpret_cast<const uint4*>(Wp + ((size_t)p * ldp + col0 + n) * K + (size_t)s * 8);
-      *reinterpret_cast<uint4*>(smem + p * plane_bytes + n * row_bytes + ((s ^ (n & 15)) * 16)) = v;
-    }
-  }
-  __syncthreads();
-
-  const int ntiles = (rows + 31) / 32, nk = K / 32;
-  // this wave's tiles: group + ngroups * (wid + NW * i)
-  const int first = group + ngroups * wid, stride = ngroups * NW;
-  const int my_tiles = first < ntiles ? (ntiles - 1 - first) / stride + 1 : 0;
-  const int F = my_tiles * nk;
-  if (F == 0) return;
-
-  auto load_a = [&](int f, float4 (&a)[4]) {
-    const int t = first + (f / nk) * stride, kt = f % nk;
-    const float* src = X + (size_t)(t * 32 + l32) * ldx + kt * 32 + lh * 16;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) a[q] = *reinterpret_cast<const float4*>(src + 4 * q);
-  };
-
-  f32x16 acc[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-
-  float4 an[4], ac[4];
-  load_a(0, an);
-  int kt = 0, tcount = 0;
-  for (int f = 0; f < F; ++f) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ac[q] = an[q];
-    if (f + 1 < F) load_a(f + 1, an);
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      bf16x8 a0, a1, a2;
-      split3(ac[2 * c], ac[2 * c + 1], a0, a1, a2);
-      const int s = 4 * kt + 2 * lh + c;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int n = j * 32 + l32;
-        const char* bp = smem + n * row_bytes + ((s ^ (n & 15)) * 16);
-        const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(bp);
-        const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(bp + plane_bytes);
-        const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(bp + 2 * plane_bytes);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[j], 0, 0, 0);
-      }
-    }
-    if (++kt == nk) {  // tile done: epilogue
-      const int t = first + tcount * stride;
-      const int rbase = t * 32 + 4 * lh;
-      const int rm0 = (C == 1) ? 0 : rbase % C;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int c = col0 + j * 32 + l32;
-        const bool cok = c < ncols;
-        const float bv = (bias && cok) ? bias[c] : 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int off = (e & 3) + 8 * (e >> 2);
-          const int r = rbase + off;
-          float v = acc[j][e];
-          acc[j][e] = 0.f;
-          if (!cok || r >= rows) continue;
-          if (bias) {
-            int tt = rm0 + off;
-            while (tt >= C) tt -= C;
-            if (tt == 0) v += bv;
-          }
-          if (HAS_R) v += R[(size_t)r * ldr + c];
-          Y[(size_t)r * ldy + c] = v;
-        }
-      }
-      kt = 0;
-      ++tcount;
-    }
-  }
-}
-
-template <int NW>
-void launch_x6p_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
-                  float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
-  const int P = (ncols + XP_BN - 1) / XP_BN;
-  const int slots = std::max(8, cu_count_x6() / 8 * 8);  // workgroups resident at once (1 per CU)
-  int ngroups = std::max(1, slots / P);
-  const int ntiles = (rows + 31) / 32;
-  ngroups = std::min(ngroups, std::max(1, (ntiles + NW - 1) / NW));
-  const int grid = round_up(ngroups * P, 8);
-  const size_t smem = 3ull * XP_BN * K * 2;
-  ensure_smem(gemm_x6p_kernel<NW, true>, smem);
-  ensure_smem(gemm_x6p_kernel<NW, false>, smem);
-  if (R)
-    hipLaunchKernelGGL((gemm_x6p_kernel<NW, true>), dim3(grid), dim3(NW * 64), smem, s, X, ldx, Wp, ldp, bias, R,
-                       ldr, Y, ldy, rows, ncols, K, C, P, ngroups);
-  else
-    hipLaunchKernelGGL((gemm_x6p_kernel<NW, false>), dim3(grid), dim3(NW * 64), smem, s, X, ldx, Wp, ldp, bias, R,
-                       ldr, Y, ldy, rows, ncols, K, C, P, ngroups);
 }
 
 // ---- persistent 16x16x32 form (round 3): 2-D wave grid, direct-from-accumulator stores -------
@@ -1620,12 +890,9 @@ void launch_x6p_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const fl
 __device__ __forceinline__ int x6m_fa(int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 2); }
 __device__ __forceinline__ int x6m_fb(int n) { return ((n >> 2) & 1) << 1; }
 
-// SPREAD: the next step's DMA pieces are issued between the first column blocks' MFMAs
-// instead of all at once after the barrier (LDS-DMA issue costs ~60 cycles a piece), and
-// the activation fragments are split just ahead of their first MFMAs.
-// ABL (tools/gemm_bench.py ablations only, wrong results): bit 0 no DMA after the first
-// stage, bit 1 no barrier, bit 2 no epilogue stores, bit 3 no activation split (hi term only)
-template <int TNC, bool HAS_R, bool SPREAD = false, int ABL = 0, bool DMA4 = false>
+// (Round 3 measurement: the next step's DMA pieces issued between the first column blocks'
+// MFMAs, instead of all at once after the barrier, were no faster.)
+template <int TNC, bool HAS_R, bool DMA4 = false>
 __global__ __launch_bounds__(512, 1) void gemm_x6m_kernel(const float* __restrict__ X, int ldx,
                                                           const uint16_t* __restrict__ Wp, int ldp,
                                                           const float* __restrict__ bias, const float* R, int ldr,
@@ -1729,11 +996,10 @@ __global__ __launch_bounds__(512, 1) void gemm_x6m_kernel(const float* __restric
     else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (!(ABL & 2)) __builtin_amdgcn_s_barrier();  // step f landed everywhere; step f-1's buffer is free
+    __builtin_amdgcn_s_barrier();  // step f landed everywhere; step f-1's buffer is free
     asm volatile("" ::: "memory");
     stored = false;
-    const bool more = f + 1 < F && !(ABL & 1);
-    if (!SPREAD && more) stage(f + 1, buf ^ 1);
+    if (f + 1 < F) stage(f + 1, buf ^ 1);
     const char* S = smem + buf * STAGE;
     // activation fragments: 4 row blocks, split once
     bf16x8 a0[4], a1[4], a2[4];
@@ -1742,14 +1008,7 @@ __global__ __launch_bounds__(512, 1) void gemm_x6m_kernel(const float* __restric
     for (int rb = 0; rb < 4; ++rb) {
       au[rb] = *reinterpret_cast<const float4*>(S + aoff[rb][0]);
       av[rb] = *reinterpret_cast<const float4*>(S + aoff[rb][1]);
-      if (ABL & 8) {
-        a0[rb] = __builtin_bit_cast(bf16x8, (u32x4v){pk_bf16(au[rb].x, au[rb].y), pk_bf16(au[rb].z, au[rb].w),
-                                                       pk_bf16(av[rb].x, av[rb].y), pk_bf16(av[rb].z, av[rb].w)});
-        a1[rb] = a0[rb];
-        a2[rb] = a0[rb];
-      } else if (!SPREAD) {
-        split3(au[rb], av[rb], a0[rb], a1[rb], a2[rb]);
-      }
+      split3(au[rb], av[rb], a0[rb], a1[rb], a2[rb]);
     }
     bf16x8 wf[2][3];
     {
@@ -1768,30 +1027,8 @@ __global__ __launch_bounds__(512, 1) void gemm_x6m_kernel(const float* __restric
         wf[(cb + 1) & 1][2] = *reinterpret_cast<const bf16x8*>(S + o + 2 * B_PLANE);
       }
       const bf16x8 b0 = wf[cb & 1][0], b1 = wf[cb & 1][1], b2 = wf[cb & 1][2];
-      if (SPREAD && more && dma_wave) {  // pieces [cb PER / HALF, (cb + 1) PER / HALF) over the first HALF blocks
-        constexpr int HALF = TNC / 2 > 0 ? TNC / 2 : 1;
-        if (cb < HALF) {
-          int row0n, col0n;
-          tile_of((f + 1) / nk, row0n, col0n);
-          const int ktn = (f + 1) % nk;
-          const char* xa = reinterpret_cast<const char*>(X + (size_t)row0n * ldx) + ktn * (BK * 4);
-          const char* wb = reinterpret_cast<const char*>(Wp + (size_t)col0n * K) + ktn * (BK * 2);
-#pragma unroll
-          for (int t = 0; t < PER; ++t) {
-            if (t * HALF / PER != cb) continue;
-            const char* base = isA[t] ? xa : wb;
-            const uint32_t dst = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)((buf ^ 1) * STAGE) + ldst[t]);
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(voff[t]), "s"(base), "s"(dst)
-                         : "memory");
-          }
-        }
-      }
 #pragma unroll
       for (int rb = 0; rb < 4; ++rb) {
-        if (SPREAD && !(ABL & 8) && cb == 0) split3(au[rb], av[rb], a0[rb], a1[rb], a2[rb]);
         f32x4 c = acc[rb][cb];
         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0, a2[rb], c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b2, a0[rb], c, 0, 0, 0);
@@ -1816,22 +1053,17 @@ __global__ __launch_bounds__(512, 1) void gemm_x6m_kernel(const float* __restric
     for (int rb = 0; rb < 4; ++rb) bfl[rb] = (bias && (rw0 + rb * 16 + l16) % C == 0) ? 1.f : 0.f;
     if (full) {
       // (no drain: the compiler's waits on the bias / residual loads also cover the older DMA).
-      // The bias values of every column block are loaded before the first store (X6M_BIAS1):
-      // a load between two stores would wait for every earlier store (vmcnt counts in order)
-#if X6M_BIAS1
+      // The bias values of every column block are loaded before the first store: a load
+      // between two stores would wait for every earlier store (vmcnt counts in order; loads
+      // between the stores: 590-597 K -> 600-602 K E_L/s hoisted, profiles/r04_epilogue_ab.txt)
       float4 bvs[TNC];
 #pragma unroll
       for (int cb = 0; cb < TNC; ++cb)
         bvs[cb] = bias ? *reinterpret_cast<const float4*>(bias + cw0 + cb * 16 + 4 * kg) : make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
 #pragma unroll
       for (int cb = 0; cb < TNC; ++cb) {
         const int n = cw0 + cb * 16 + 4 * kg;
-#if X6M_BIAS1
         const float4 bv = bvs[cb];
-#else
-        const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
         float4 rv[4];
         if (HAS_R) {
 #pragma unroll
@@ -1851,20 +1083,16 @@ __global__ __launch_bounds__(512, 1) void gemm_x6m_kernel(const float* __restric
             c[2] += rv[rb].z;
             c[3] += rv[rb].w;
           }
-          if (!(ABL & 4) || c[0] == 1.2345e-30f) {
-            f32x4* yp = reinterpret_cast<f32x4*>(Y + (size_t)(rw0 + rb * 16 + l16) * ldy + n);
-            if constexpr (X6M_NT)
-              __builtin_nontemporal_store(c, yp);  // streaming: the weights stay resident in L2
-            else
-              *yp = c;
-          }
+          // plain stores: nontemporal ones cut the weight re-fetch (FETCH 652 -> 464 MB per launch) but
+          // cost the attention that reads q|k|v more, C2 812.6 -> 807.6 K (profiles/r06_v29_x6m_nt_ab.txt)
+          *reinterpret_cast<f32x4*>(Y + (size_t)(rw0 + rb * 16 + l16) * ldy + n) = c;
         }
       }
 #pragma unroll
       for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
         for (int cb = 0; cb < TNC; ++cb) acc[rb][cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      stored = !(ABL & 4);
+      stored = true;
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
@@ -1890,7 +1118,7 @@ __global__ __launch_bounds__(512, 1) void gemm_x6m_kernel(const float* __restric
   }
 }
 
-template <int TNC, bool SPREAD = false, int ABL = 0, bool DMA4 = false>
+template <int TNC, bool DMA4 = false>
 void launch_x6m_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
                   float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
   constexpr int BM = 256, BN = 32 * TNC;
@@ -1899,12 +1127,12 @@ void launch_x6m_t(const float* X, int ldx, const uint16_t* Wp, int ldp, const fl
   int grid = std::min(ntm * ntn, cu_count_x6());
   grid = std::max(8, grid / 8 * 8);
   if (R) {
-    ensure_smem(gemm_x6m_kernel<TNC, true, SPREAD, ABL, DMA4>, smem);
-    hipLaunchKernelGGL((gemm_x6m_kernel<TNC, true, SPREAD, ABL, DMA4>), dim3(grid), dim3(512), smem, s, X, ldx, Wp, ldp, bias, R,
+    ensure_smem(gemm_x6m_kernel<TNC, true, DMA4>, smem);
+    hipLaunchKernelGGL((gemm_x6m_kernel<TNC, true, DMA4>), dim3(grid), dim3(512), smem, s, X, ldx, Wp, ldp, bias, R,
                        ldr, Y, ldy, rows, ncols, K, C, ntm, ntn);
   } else {
-    ensure_smem(gemm_x6m_kernel<TNC, false, SPREAD, ABL, DMA4>, smem);
-    hipLaunchKernelGGL((gemm_x6m_kernel<TNC, false, SPREAD, ABL, DMA4>), dim3(grid), dim3(512), smem, s, X, ldx, Wp, ldp, bias,
+    ensure_smem(gemm_x6m_kernel<TNC, false, DMA4>, smem);
+    hipLaunchKernelGGL((gemm_x6m_kernel<TNC, false, DMA4>), dim3(grid), dim3(512), smem, s, X, ldx, Wp, ldp, bias,
                        R, ldr, Y, ldy, rows, ncols, K, C, ntm, ntn);
   }
 }
@@ -1959,11 +1187,10 @@ struct ChainArgs {
 // Same products in the same order as the other x6 kernels; the LayerNorm statistics are
 // summed in a different order (f32 rounding, not bitwise).
 constexpr int CS_NW = 8, CS_RB = CH_BM / 32, CS_PD = 4, CS_LSP = 264;  // plane row: 528 B
-#ifndef CHAIN_PRM  // A/B knob: LN1 / LN2 scale-shift and the P2 bias staged in LDS once per tile
-#define CHAIN_PRM 1
-#endif
-// CS_PRMF: [ln1 gamma | beta][b2][ln2 gamma | beta] floats after the partials (CHAIN_PRM)
-constexpr int CS_PRMF = CHAIN_PRM ? 5 * 256 : 0;
+// CS_PRMF: [ln1 gamma | beta][b2][ln2 gamma | beta] floats after the partials, staged in LDS
+// once per tile instead of global loads inside the epilogues behind the next pass's weight
+// prefetch (583-586 K -> 592-593 K E_L/s, profiles/r04_chain_prm_ab.txt)
+constexpr int CS_PRMF = 5 * 256;
 constexpr size_t CS_PLANE = (size_t)CH_BM * CS_LSP * 2, CS_SMEM = 3 * CS_PLANE + 2 * CS_NW * CH_BM * 4 + CS_PRMF * 4;
 static_assert(CS_SMEM <= 163840, "chain LDS");
 
@@ -2001,7 +1228,7 @@ __global__ __launch_bounds__(512) void chain_x6s_kernel(ChainArgs a) {
   extern __shared__ float4 smem4[];
   char* smem = reinterpret_cast<char*>(smem4);
   float* part = reinterpret_cast<float*>(smem + 3 * CS_PLANE);  // [2][8 waves][96 rows]
-  float* prm = part + 2 * CS_NW * CH_BM;                         // CHAIN_PRM: [ln1 | b2 | ln2]
+  float* prm = part + 2 * CS_NW * CH_BM;                         // [ln1 | b2 | ln2]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l32 = lane & 31, lh = lane >> 5;
@@ -2016,21 +1243,16 @@ __global__ __launch_bounds__(512) void chain_x6s_kernel(ChainArgs a) {
   const int row0 = bid * TRW, rows = min(a.rows, row0 + TRW);
   // every barrier of this kernel orders LDS only (planes, partial sums, staging); no wave reads
   // global memory another wave of the launch wrote, so the VMEM queue (weight prefetch, h / Y3
-  // stores) may stay in flight across it
+  // stores) may stay in flight across it (against __syncthreads' vmcnt(0): local energy
+  // -0.03 ms, profiles/r05_v12_lbar_ab.txt)
   auto lbar = []() __attribute__((always_inline)) {
-#if CHAIN_LBAR
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#else
-    __syncthreads();
-#endif
   };
   CHAIN_T(0);
-  if (CHAIN_PRM) {  // read before the prologue's barrier
-    for (int q = tid; q < 5 * 256; q += 512)
-      prm[q] = q < 512 ? a.ln1[q] : (q < 768 ? a.b2[q - 512] : a.ln2[q - 768]);
-  }
+  for (int q = tid; q < CS_PRMF; q += 512)  // read before the prologue's barrier
+    prm[q] = q < 512 ? a.ln1[q] : (q < 768 ? a.b2[q - 512] : a.ln2[q - 768]);
   // plane p, tile row r, column c (bf16 units)
   auto pl = [&](int p, int r, int c) __attribute__((always_inline)) {
     return smem + (size_t)p * CS_PLANE + (size_t)r * (LSP * 2) + c * 2;
@@ -2069,7 +1291,7 @@ __global__ __launch_bounds__(512) void chain_x6s_kernel(ChainArgs a) {
 #pragma unroll
       for (int p = 0; p < 3; ++p) bq[d][p] = *reinterpret_cast<const bf16x8*>(wr + p * plane + 16 * d);
   };
-  // TR: the operands swapped, D[tile row][output column] (P3's store layout, CHAIN_P3T)
+  // TR: the operands swapped, D[tile row][output column] (P3's store layout)
   // accumulate_: keep acc's contents (layer 1's residual pass, NA > 0) instead of starting from 0
   auto gemm = [&](auto tr_, auto nkt_, auto accumulate_) __attribute__((always_inline)) {
     constexpr bool TR = decltype(tr_)::value;
@@ -2132,18 +1354,19 @@ __global__ __launch_bounds__(512) void chain_x6s_kernel(ChainArgs a) {
     }
   };
   using NoTr = std::integral_constant<bool, false>;
+  using Tr = std::integral_constant<bool, true>;
   using Zero = std::integral_constant<bool, false>;
   using Accum = std::integral_constant<bool, true>;
   // MFMA layout: reg 4 g + e of acc[rb] = tile row 32 rb + l32, column 32 wid + 8 g + 4 lh + e
   auto colof = [&](int g) __attribute__((always_inline)) { return 32 * wid + 8 * g + 4 * lh; };
-  // LayerNorm of the values x (MFMA layout, 16 per lane and row block) in registers:
-  // two-pass mean / centred variance (eps 1e-5); the 8 wave partials of a row meet in LDS
+  // LayerNorm of the values x (MFMA layout, 16 per lane and row block) in registers
+  // (eps 1e-5); the 8 wave partials of a row meet in LDS
   float x[RB][16];
   auto layernorm = [&](const float* ln) __attribute__((always_inline)) {
-#if CHAIN_LN1P
     // ONE statistics round: sum x and sum x^2 together (flax's fast variance, the reference's
     // own arithmetic: var = max(E[x^2] - E[x]^2, 0), oracle/reference.py:134-137), one barrier
     // and one LDS exchange per LayerNorm instead of the two of the centred two-pass form
+    // (two-pass: 646-647 K E_L/s, mcmc_step 2.60 ms; profiles/r05_v2_ab.txt)
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
       float t = 0.f, q = 0.f;
@@ -2182,50 +1405,6 @@ __global__ __launch_bounds__(512) void chain_x6s_kernel(ChainArgs a) {
         x[rb][4 * g + 3] = gm.w * (rs * (x[rb][4 * g + 3] - mean)) + bt.w;
       }
     }
-#else
-    float s[RB];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-      float t = 0.f;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) t += (x[rb][4 * g] + x[rb][4 * g + 1]) + (x[rb][4 * g + 2] + x[rb][4 * g + 3]);
-      t += __shfl_xor(t, 32, 64);
-      if (lh == 0) part[wid * CH_BM + 32 * rb + l32] = t;
-    }
-    lbar();
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-      float t = 0.f;
-#pragma unroll
-      for (int w = 0; w < CS_NW; ++w) t += part[w * CH_BM + 32 * rb + l32];
-      s[rb] = t * (1.f / 256.f);
-      float q = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        x[rb][e] -= s[rb];
-        q += x[rb][e] * x[rb][e];
-      }
-      q += __shfl_xor(q, 32, 64);
-      if (lh == 0) part[(CS_NW + wid) * CH_BM + 32 * rb + l32] = q;
-    }
-    lbar();
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-      float t = 0.f;
-#pragma unroll
-      for (int w = 0; w < CS_NW; ++w) t += part[(CS_NW + w) * CH_BM + 32 * rb + l32];
-      const float rs = __builtin_amdgcn_rsqf(t * (1.f / 256.f) + 1e-5f);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 gm = *reinterpret_cast<const float4*>(ln + colof(g));
-        const float4 bt = *reinterpret_cast<const float4*>(ln + CH_BN + colof(g));
-        x[rb][4 * g] = gm.x * (rs * x[rb][4 * g]) + bt.x;
-        x[rb][4 * g + 1] = gm.y * (rs * x[rb][4 * g + 1]) + bt.y;
-        x[rb][4 * g + 2] = gm.z * (rs * x[rb][4 * g + 2]) + bt.z;
-        x[rb][4 * g + 3] = gm.w * (rs * x[rb][4 * g + 3]) + bt.w;
-      }
-    }
-#endif
   };
 
   // ---- P1 prologue: o rows -> planes (each element split once)
@@ -2515,7 +1694,7 @@ __global__ __launch_bounds__(512) void chain_x6s_kernel(ChainArgs a) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) x[rb][e] = acc[rb][e];
   } else {
-  layernorm(CHAIN_PRM ? prm : a.ln1);  // its barriers: every wave is past its GEMM reads of the planes
+  layernorm(prm);  // its barriers: every wave is past its GEMM reads of the planes
   CHAIN_T(4);
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
@@ -2532,21 +1711,18 @@ __global__ __launch_bounds__(512) void chain_x6s_kernel(ChainArgs a) {
   for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const float4 bv = *reinterpret_cast<const float4*>((CHAIN_PRM ? prm + 512 : a.b2) + colof(g));
+      const float4 bv = *reinterpret_cast<const float4*>(prm + 512 + colof(g));
       const float4 h1 = get4(32 * rb + l32, colof(g));
-#if CHAIN_TANH_EXP
-      auto th = [](float z) { return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * z) + 1.f); };
-#else
-      auto th = [](float z) { return tanh_rat(z); };
-#endif
-      x[rb][4 * g] = h1.x + th(acc[rb][4 * g] + bv.x);
-      x[rb][4 * g + 1] = h1.y + th(acc[rb][4 * g + 1] + bv.y);
-      x[rb][4 * g + 2] = h1.z + th(acc[rb][4 * g + 2] + bv.z);
-      x[rb][4 * g + 3] = h1.w + th(acc[rb][4 * g + 3] + bv.w);
+      // tanh_rat is the reference's own arithmetic; the exp form 1 - 2 / (exp(2x) + 1) left the
+      // step time unchanged (profiles/r04_epilogue_ab.txt)
+      x[rb][4 * g] = h1.x + tanh_rat(acc[rb][4 * g] + bv.x);
+      x[rb][4 * g + 1] = h1.y + tanh_rat(acc[rb][4 * g + 1] + bv.y);
+      x[rb][4 * g + 2] = h1.z + tanh_rat(acc[rb][4 * g + 2] + bv.z);
+      x[rb][4 * g + 3] = h1.w + tanh_rat(acc[rb][4 * g + 3] + bv.w);
     }
   }
   CHAIN_T(7);
-  layernorm(CHAIN_PRM ? prm + 768 : a.ln2);
+  layernorm(prm + 768);
   CHAIN_T(8);
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) {
@@ -2564,68 +1740,38 @@ __global__ __launch_bounds__(512) void chain_x6s_kernel(ChainArgs a) {
   // ---- P3: Y3 = h2 W3 + b3, 256-column passes (a wave past n3 idles), MFMA-layout stores
   for (int col0 = 0; col0 < a.n3; col0 += CH_BN) {
     if (col0 + 32 * wid >= a.n3) continue;  // wave-uniform
-    gemm(std::integral_constant<bool, CHAIN_P3T != 0>{}, K16{}, Zero{});
+    gemm(Tr{}, K16{}, Zero{});
     if (col0 < 3 * CH_BN) CHAIN_T(10 + 2 * (col0 / CH_BN));
-#if CHAIN_P3T
-    {  // D[tile row][column]: reg q of acc[rb] = row 32 rb + (q & 3) + 8 (q >> 2) + 4 lh, column l32.
-      // Buffer stores: the tile's rows as the resource, one 32-bit lane offset (past the range off
-      // n3); full tiles put the row offset in soffset, the partial last tile in voffset
-      const int c = col0 + 32 * wid + l32;
-      const bool cok = c < a.n3;
-      const float bv = cok ? a.b3[c] : 0.f;
-      if (col0 + CH_BN + 32 * wid < a.n3) prefetch(a.Wp3, a.ldp3, col0 + CH_BN, K16{});
-      const int nrow = min(CH_BM, rows - row0), ldb = a.ldy3 * 4;
-      const auto rs = __builtin_amdgcn_make_buffer_rsrc(a.Y3 + (size_t)row0 * a.ldy3, (short)0, nrow * ldb, 0x00020000);
-      const int vo = cok ? 4 * lh * ldb + 4 * c : 0x7fffffff;
-      if (nrow == CH_BM) {  // full tile: the row offset in soffset (every row inside the resource)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-#pragma unroll
-          for (int q = 0; q < 16; ++q)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, acc[rb][q] + bv), rs, vo,
-                                                  (32 * rb + (q & 3) + 8 * (q >> 2)) * ldb, 0);
-        }
-      } else {  // the last, partial tile: the raw-buffer range check covers voffset only (not
-        // soffset), so the row goes into voffset and rows past the batch are out of range
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            const int r = 32 * rb + (q & 3) + 8 * (q >> 2) + 4 * lh;
-            const int v = (cok && r < nrow) ? 4 * c + r * ldb : 0x7fffffff;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, acc[rb][q] + bv), rs, v, 0, 0);
-          }
-        }
-      }
-      if (col0 < 3 * CH_BN) CHAIN_T(11 + 2 * (col0 / CH_BN));
-      continue;
-    }
-#endif
-    // this lane's 16 bias values first (one wait), THEN the prefetch and the stores: a bias load
-    // between two stores waits for every earlier store (vmcnt counts in order)
-    float4 b3v[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int c = col0 + colof(g);
-      b3v[g] = CHAIN_P3B && c + 3 < a.n3 ? *reinterpret_cast<const float4*>(a.b3 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    // D[tile row][column]: reg q of acc[rb] = row 32 rb + (q & 3) + 8 (q >> 2) + 4 lh, column l32
+    // (the MFMA operands swapped): one register = two 128-B row segments, full-rate dword stores;
+    // float4 stores of 32 rows x 32 B per instruction: 643-648 K against 652-660 K E_L/s,
+    // profiles/r05_v5_ab.txt.
+    // Buffer stores: the tile's rows as the resource, one 32-bit lane offset (past the range off
+    // n3); full tiles put the row offset in soffset, the partial last tile in voffset
+    const int c = col0 + 32 * wid + l32;
+    const bool cok = c < a.n3;
+    const float bv = cok ? a.b3[c] : 0.f;
     if (col0 + CH_BN + 32 * wid < a.n3) prefetch(a.Wp3, a.ldp3, col0 + CH_BN, K16{});
+    const int nrow = min(CH_BM, rows - row0), ldb = a.ldy3 * 4;
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc(a.Y3 + (size_t)row0 * a.ldy3, (short)0, nrow * ldb, 0x00020000);
+    const int vo = cok ? 4 * lh * ldb + 4 * c : 0x7fffffff;
+    if (nrow == CH_BM) {  // full tile: the row offset in soffset (every row inside the resource)
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-      const int r = row0 + 32 * rb + l32;
-      if (r >= rows) continue;
-      float* yr = a.Y3 + (size_t)r * a.ldy3;
+      for (int rb = 0; rb < RB; ++rb) {
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int c = col0 + colof(g);
-        if (c + 3 < a.n3) {
-          const float4 bv = CHAIN_P3B ? b3v[g] : *reinterpret_cast<const float4*>(a.b3 + c);
-          *reinterpret_cast<float4*>(yr + c) = make_float4(acc[rb][4 * g] + bv.x, acc[rb][4 * g + 1] + bv.y,
-                                                           acc[rb][4 * g + 2] + bv.z, acc[rb][4 * g + 3] + bv.w);
-        } else {
+        for (int q = 0; q < 16; ++q)
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, acc[rb][q] + bv), rs, vo,
+                                                (32 * rb + (q & 3) + 8 * (q >> 2)) * ldb, 0);
+      }
+    } else {  // the last, partial tile: the raw-buffer range check covers voffset only (not
+      // soffset), so the row goes into voffset and rows past the batch are out of range
 #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (c + e < a.n3) yr[c + e] = acc[rb][4 * g + e] + a.b3[c + e];
+      for (int rb = 0; rb < RB; ++rb) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int r = 32 * rb + (q & 3) + 8 * (q >> 2) + 4 * lh;
+          const int v = (cok && r < nrow) ? 4 * c + r * ldb : 0x7fffffff;
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, acc[rb][q] + bv), rs, v, 0, 0);
         }
       }
     }
@@ -2647,225 +1793,71 @@ void launch_split_planes(const float* Wt, int ldw, int ncols, int K, uint16_t* W
 
 bool gemm_x6_supported(int K) { return K % X6_BK == 0; }
 
-void launch_gemm_x6_variant(int v, const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias,
+namespace {
+using X6Launch = void (*)(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R,
+                          int ldr, float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s);
+template <int TN, int NW, int ST, int WN = 1>
+void launch_x6d_plain(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
+                      float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
+  launch_x6d_t<TN, NW, ST, 0, WN>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
+}
+// 96 x 256 tiles of 3 x 4 waves when round_up(rows, 96) stays inside round_up(rows, 256), else 64 x 256
+void launch_x6d_grid96(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
+                       float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
+  if (round_up(rows, 96) <= round_up(rows, 256))
+    launch_x6d_plain<2, 3, 3, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
+  else
+    launch_x6d_plain<2, 2, 3, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
+}
+// Every form there is: the eight launch_gemm_x6 picks from (X6Form, dh_internal.h), and by
+// bare code the tiles beside them that the kernel tests and tools/ still compare them with.
+const struct {
+  int code;
+  X6Launch launch;
+} kX6Forms[] = {
+    // gemm_x6d, two workgroups per CU: 128 x 32*TN (NW = 4) / 256 x 32*TN tiles, two buffers
+    {X6D_128x192, launch_x6d_plain<6, 4, 2>},
+    {X6D_256x128, launch_x6d_plain<4, 8, 2>},
+    {43, launch_x6d_plain<8, 4, 2>},
+    {45, launch_x6d_plain<4, 4, 2>},
+    // gemm_x6d, 256 x 32*TN tiles, three buffers
+    {40, launch_x6d_plain<8, 8, 3>},
+    {41, launch_x6d_plain<6, 8, 3>},
+    // gemm_x6d, 2-D wave grids, 256-column tiles (ncols % 4 == 0): 96 (or 64), 64, 128 rows
+    {60, launch_x6d_grid96},
+    {61, launch_x6d_plain<2, 2, 3, 4>},
+    {62, launch_x6d_plain<2, 4, 3, 4>},
+    // gemm_x6q, persistent lean; 56-58 with the B fragment reads pipelined one column block ahead
+    {50, launch_x6q_t<8>},
+    {51, launch_x6q_t<6>},
+    {X6Q_256x128, launch_x6q_t<4>},
+    {X6Q_256x256, launch_x6q_t<8, true>},
+    {X6Q_256x192, launch_x6q_t<6, true>},
+    {X6Q_256x160, launch_x6q_t<5, true>},
+    // gemm_x6m, persistent 16x16x32 form; 76, 77, 79, 90 with the DMA from the column-half-0 waves only
+    {80, launch_x6m_t<8>},
+    {81, launch_x6m_t<6>},
+    {82, launch_x6m_t<5>},
+    {83, launch_x6m_t<4>},
+    {X6M_256x256, launch_x6m_t<8, true>},
+    {X6M_256x192, launch_x6m_t<6, true>},
+    {79, launch_x6m_t<4, true>},
+    {90, launch_x6m_t<5, true>},
+};
+}  // namespace
+
+bool launch_gemm_x6_variant(int v, const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias,
                             const float* R, int ldr, float* Y, int ldy, int rows, int ncols, int K, int C,
                             hipStream_t s) {
-  switch (v) {
-    case 1:
-      launch_x6_t<4, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 2:
-      launch_x6_t<4, 8>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 3:
-      launch_x6_t<8, 6>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 4:
-      launch_x6_t<4, 6>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 5:
-      launch_x6_t<2, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 6:
-      launch_x6_t<2, 8>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 7:
-      launch_x6_t<8, 2>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // persistent, weight panel resident in LDS (K <= 256)
-    case 10:
-      launch_x6p_t<8>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 11:
-      launch_x6p_t<12>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 12:
-      launch_x6p_t<16>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 13:
-      launch_x6p_t<4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // big tiles 256 x 64*TN, BK = 16
-    case 20:
-      launch_x6b_t<4, 3>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 21:
-      launch_x6b_t<4, 2>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 22:
-      launch_x6b_t<3, 3>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 23:
-      launch_x6b_t<2, 3>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // pipelined 256 x 32*TN
-    case 30:
-      launch_x6c_t<8>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 31:
-      launch_x6c_t<6>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 32:
-      launch_x6c_t<4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // lean pipelined 256 x 32*TN
-    case 40:
-      launch_x6d_t<8>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 41:
-      launch_x6d_t<6>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 42:
-      launch_x6d_t<4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // two workgroups per CU: 128 x 32*TN tiles, two buffers
-    case 43:
-      launch_x6d_t<8, 0, 4, 2>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 44:
-      launch_x6d_t<6, 0, 4, 2>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 45:
-      launch_x6d_t<4, 0, 4, 2>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 46:
-      launch_x6d_t<4, 0, 8, 2>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // 2-D wave grids, 256-column tiles (ncols % 4 == 0): 96 x 256 of 3 x 4 waves (when
-    // round_up(rows, 96) stays inside round_up(rows, 256), else 64 x 256), 64 x 256 of
-    // 2 x 4 waves, 128 x 256 of 4 x 4 waves
-    case 60:
-      if (round_up(rows, 96) <= round_up(rows, 256)) {
-        launch_x6d_t<2, 0, 3, 3, 0, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-        break;
-      }
-      [[fallthrough]];
-    case 61:
-      launch_x6d_t<2, 0, 2, 3, 0, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 62:
-      launch_x6d_t<2, 0, 4, 3, 0, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // deeper rings (ST - 2 stages in flight): 96 x 256 of 3 x 4 waves, 128 x 192 / 256 x 128
-    case 70:
-      if (round_up(rows, 96) <= round_up(rows, 256)) {
-        launch_x6d_t<2, 0, 3, 5, 0, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-        break;
-      }
-      [[fallthrough]];
-    case 71:
-      launch_x6d_t<6, 0, 4, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 72:
-      launch_x6d_t<6, 0, 4, 5>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 73:
-      launch_x6d_t<4, 0, 8, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 74:
-      launch_x6d_t<8, 0, 4, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 75:
-      launch_x6d_t<4, 0, 4, 5>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // persistent lean
-    case 50:
-      launch_x6q_t<8>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 51:
-      launch_x6q_t<6>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 52:
-      launch_x6q_t<4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // persistent lean, 4-stage ring (two stages in flight)
-    case 53:
-      launch_x6q_t<8, true>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 55:
-      launch_x6q_t<5>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // persistent lean with the B fragment reads pipelined one column block ahead
-    case 56:
-      launch_x6q_t<8, false, 0, true>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 57:
-      launch_x6q_t<6, false, 0, true>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 58:
-      launch_x6q_t<5, false, 0, true>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // persistent 16x16x32 form, 2-D wave grid (round 3)
-    case 80:
-      launch_x6m_t<8>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 81:
-      launch_x6m_t<6>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 82:
-      launch_x6m_t<5>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 83:
-      launch_x6m_t<4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 84:
-      launch_x6m_t<8, true>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 85:
-      launch_x6m_t<6, true>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 76:  // DMA from the column-half-0 waves only
-      launch_x6m_t<8, false, 0, true>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 77:
-      launch_x6m_t<6, false, 0, true>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 78:  // DMA4 + spread issue
-      launch_x6m_t<8, true, 0, true>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 79:
-      launch_x6m_t<4, false, 0, true>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 90:
-      launch_x6m_t<5, false, 0, true>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    // ablations of 80 (wrong results; tools/gemm_bench.py only): cumulative
-    case 86:
-      launch_x6m_t<8, false, 1>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 87:
-      launch_x6m_t<8, false, 3>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 88:
-      launch_x6m_t<8, false, 7>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 89:
-      launch_x6m_t<8, false, 15>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 95:  // ablation of 50: no epilogue stores (wrong results; tools/gemm_bench.py only)
-      launch_x6q_t<8, false, 1>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-
-    // ablations of variant 40 (wrong results; tools/gemm_bench.py only)
-    case 91:
-      launch_x6d_t<8, 1>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 92:
-      launch_x6d_t<8, 2>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 93:
-      launch_x6d_t<8, 3>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    case 94:
-      launch_x6d_t<8, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-      break;
-    default:
-      launch_x6_t<8, 4>(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
-  }
+  for (const auto& f : kX6Forms)
+    if (f.code == v) {
+      f.launch(X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
+      return true;
+    }
+  return false;
 }
 
-void launch_gemm_x6(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
-                    float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
+int gemm_x6_choose(int rows, int ncols) {
   // measured on MI355X (tools/gemm_bench.py, K = 256): channel rows take the persistent lean
   // kernel with 256 x 256 tiles (256 x 192 when ncols is a multiple of 192 only); short
   // (log-psi) row counts take 256 x 128 tiles, two workgroups per CU (128 x 192 when ncols
@@ -2881,13 +1873,13 @@ void launch_gemm_x6(const float* X, int ldx, const uint16_t* Wp, int ldp, const 
   // tiles over 256 CUs) stays on gemm_x6q (394 vs 404 us).
   int v;
   if (rows >= 65536 && ncols % 256 == 0 && ncols >= 512) {
-    v = 76;
+    v = X6M_256x256;
   } else if (rows >= 65536 && ncols == 192) {
-    v = 77;
+    v = X6M_256x192;
   } else if (rows >= 65536) {
-    v = 56;
+    v = X6Q_256x256;
     if (ncols < 1024) {
-      const int tns[4] = {8, 6, 5, 4}, vs[4] = {56, 57, 58, 52};
+      const int tns[4] = {8, 6, 5, 4}, vs[4] = {X6Q_256x256, X6Q_256x192, X6Q_256x160, X6Q_256x128};
       int best = round_up(ncols, 256);
       for (int q = 1; q < 4; ++q) {
         const int padded = round_up(ncols, 32 * tns[q]);
@@ -2898,44 +1890,29 @@ void launch_gemm_x6(const float* X, int ldx, const uint16_t* Wp, int ldp, const 
       }
     }
   } else {
-    v = (ncols % 192 == 0) ? 44 : 46;
+    v = (ncols % 192 == 0) ? X6D_128x192 : X6D_256x128;
   }
-  launch_gemm_x6_variant(v, X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
+  return v;
 }
 
+void launch_gemm_x6(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* R, int ldr,
+                    float* Y, int ldy, int rows, int ncols, int K, int C, hipStream_t s) {
+  launch_gemm_x6_variant(gemm_x6_choose(rows, ncols), X, ldx, Wp, ldp, bias, R, ldr, Y, ldy, rows, ncols, K, C, s);
+}
 
 // log-psi GEMM + LayerNorm (LNM 1 / 2 above), in place over h [rows][256].  Form nw:
 //   0 = choose; 3 / 4 = 96 / 128-row tiles of 32 x 256 wave blocks (3 / 4 waves);
 //   1 = 96-row tiles of 3 x 4 waves with 32 x 64 blocks (12 waves, all four SIMDs busy);
-//   2 = 64-row tiles of 2 x 4 waves; 8 = 128-row tiles of 4 x 4 waves.
+//   2 = 64-row tiles of 2 x 4 waves; 8 = 128-row tiles of 4 x 4 waves;
+//   any other: false, nothing launched.
 // One workgroup per CU (LDS).  Callers pad X and h to kWalkerRowPad (768 = lcm(96, 256))
 // rows, so no tile reads past them.
-void launch_gemm_x6_ln(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* ln,
+bool launch_gemm_x6_ln(const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias, const float* ln,
                        float* h, int rows, int K, int mode, int nw, hipStream_t s, X6Feat feat) {
   if (mode != 0) feat = X6Feat{};
-  if (nw >= 32) {  // tools/ln_gemm_bench.py only: ablations / forced forms (caller pads rows to 768)
-    switch (nw) {
-#define DH_X6LN_A(TNV, NWV, WNV, ABLV)                                                                      \
-  launch_x6d_t<TNV, ABLV, NWV, 3, 2, WNV>(X, ldx, Wp, ldp, bias, h, 256, h, 256, rows, 256, K, 1, s, ln)
-      case 32: DH_X6LN_A(2, 2, 4, 1); break;
-      case 33: DH_X6LN_A(2, 2, 4, 2); break;
-      case 34: DH_X6LN_A(2, 2, 4, 3); break;
-      case 35: DH_X6LN_A(2, 2, 4, 4); break;
-      case 36: DH_X6LN_A(2, 3, 4, 0); break;
-      case 37: DH_X6LN_A(2, 3, 4, 4); break;
-      case 38: DH_X6LN_A(2, 4, 4, 0); break;
-      case 39: DH_X6LN_A(2, 4, 4, 4); break;
-      case 40: DH_X6LN_A(2, 2, 4, 5); break;
-      case 41: DH_X6LN_A(2, 3, 4, 5); break;
-      case 42: DH_X6LN_A(2, 3, 4, 6); break;
-      case 43: DH_X6LN_A(2, 3, 4, 7); break;
-#undef DH_X6LN_A
-    }
-    return;
-  }
   if (nw == 0) {
     // one workgroup per CU: the launch runs in rounds of cu_count tiles, so take the tile
-    // height with the least rounds x per-round time (MI355X, tools/ln_gemm_ablate.py:
+    // height with the least rounds x per-round time (MI355X, profiles/r02_ln_gemm_ablate.txt:
     // 64 / 96 / 128-row tiles ~23 / 28 / 30.5 us a round at K = 256; C2 24576 rows -> 96,
     // C4 40960 -> 96, C5 81920 -> 128)
     const int cus = cu_count_x6();
@@ -2949,33 +1926,23 @@ void launch_gemm_x6_ln(const float* X, int ldx, const uint16_t* Wp, int ldp, con
       }
     }
   }
-  if (nw < 1 || nw > 8) nw = 1;
-#define DH_X6LN_ST(TNV, NWV, WNV, STV)                                                                      \
-  do {                                                                                                      \
-    if (mode == 0)                                                                                          \
-      launch_x6d_t<TNV, 0, NWV, STV, 1, WNV>(X, ldx, Wp, ldp, bias, h, 256, h, 256, rows, 256, K, 1, s, ln, feat); \
-    else                                                                                                    \
-      launch_x6d_t<TNV, 0, NWV, STV, 2, WNV>(X, ldx, Wp, ldp, bias, h, 256, h, 256, rows, 256, K, 1, s, ln); \
-  } while (0)
-#define DH_X6LN(TNV, NWV, WNV)                                                                              \
-  do {                                                                                                      \
-    if (mode == 0)                                                                                          \
-      launch_x6d_t<TNV, 0, NWV, 3, 1, WNV>(X, ldx, Wp, ldp, bias, h, 256, h, 256, rows, 256, K, 1, s, ln, feat); \
-    else                                                                                                    \
-      launch_x6d_t<TNV, 0, NWV, 3, 2, WNV>(X, ldx, Wp, ldp, bias, h, 256, h, 256, rows, 256, K, 1, s, ln); \
+#define DH_X6LN(TNV, NWV, WNV)                                                                               \
+  do {                                                                                                       \
+    if (mode == 0)                                                                                           \
+      launch_x6d_t<TNV, NWV, 3, 1, WNV>(X, ldx, Wp, ldp, bias, h, 256, h, 256, rows, 256, K, 1, s, ln, feat); \
+    else                                                                                                     \
+      launch_x6d_t<TNV, NWV, 3, 2, WNV>(X, ldx, Wp, ldp, bias, h, 256, h, 256, rows, 256, K, 1, s, ln);      \
   } while (0)
   switch (nw) {
     case 1: DH_X6LN(2, 3, 4); break;
     case 2: DH_X6LN(2, 2, 4); break;
     case 3: DH_X6LN(8, 3, 1); break;
-    case 5: DH_X6LN_ST(2, 3, 4, 5); break;
-    case 6: DH_X6LN_ST(2, 3, 4, 4); break;
-    case 7: DH_X6LN_ST(2, 2, 4, 5); break;
+    case 4: DH_X6LN(8, 4, 1); break;
     case 8: DH_X6LN(2, 4, 4); break;
-    default: DH_X6LN(8, 4, 1);
+    default: return false;
   }
 #undef DH_X6LN
-#undef DH_X6LN_ST
+  return true;
 }
 
 // Chained log-psi layer tail (chain_x6s_kernel above).  X1 and h padded to kWalkerRowPad

@@ -331,10 +331,15 @@ size_t dh_debug_f_offset(const dh_handle* h, int B, int op);
  * for every harmonic p < M (norm 1, the kernels' gauge kappa = env_gauge(cos theta)) into
  * out[n][M][10]; sq = 1: integer powers by squaring (the production form), 0: powf. */
 int dh_debug_env_leaf(const float* thph, int n, int M, int sq, float* out, void* stream);
-/* Test hook: one launch of GEMM kernel variant `variant` (-1 = default):
+/* Test hook: one launch of GEMM kernel variant `variant`:
  * Y = X W (+ bias on rows r % C == 0) (+ R).  X must hold round_up(rows, 256) rows.
- * variant >= 100 selects the NT kernels: W is then the TRANSPOSED weight Wt[n][k]
- * (row stride ldw) holding round_up(ncols, 256) rows, and K % 32 == 0. */
+ * Valid codes: the register-staged tiles 0 .. 11 but 3 (production: 9, 10; -1 = 0), and the
+ * NT kernels 100 .. 107, three-stage 110, 111, 114 .. 117 (production: 104, 106, 107) and
+ * persistent 120 .. 126 (production: 120, 125; whole tiles written, Y padded to 256 rows and
+ * 256 columns).
+ * With a code >= 100, W is the TRANSPOSED weight Wt[n][k] (row stride ldw) holding
+ * round_up(ncols, 256) rows, and K % 32 == 0.  Any other code: DH_EINVAL, checked before any
+ * pointer is used. */
 int dh_debug_gemm(int variant, const float* X, int ldx, const float* W, int ldw, const float* bias, const float* R,
                   int ldr, float* Y, int ldy, int rows, int ncols, int K, int C, void* stream);
 
@@ -347,7 +352,9 @@ int dh_debug_gemm_ln(int mode, int bm, const float* X, int ldx, const float* Wt,
 
 /* Split-bf16 form of dh_debug_gemm_ln (weight as the planes of dh_debug_split_planes,
  * ldp >= dh_debug_x6_plane_rows(256)); nw = tile form: 1 = 96 rows x (3 x 4 waves),
- * 2 = 64 rows x (2 x 4 waves), 3 / 4 = 96 / 128 rows of whole-row waves, 0 = choose. */
+ * 2 = 64 rows x (2 x 4 waves), 8 = 128 rows x (4 x 4 waves), 3 / 4 = 96 / 128 rows of
+ * whole-row waves, 0 = choose (among 1, 2, 8).  Any other nw:
+ * DH_EINVAL, checked before any pointer is used. */
 int dh_debug_gemm_x6_ln(int mode, int nw, const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias,
                         const float* ln, float* h, int rows, int K, void* stream);
 /* Chained log-psi layer tail (gemm_x6.hip chain_x6_kernel; D = K = 256, rows padded to 768):
@@ -365,7 +372,13 @@ int dh_debug_gemm_lnch(int N, int mode, const float* X, const uint16_t* Wp, int 
 /* Test hooks of the split-bf16 GEMM (gemm_x6.hip): the transposed weight Wt[ncols][K]
  * is split into three bf16 planes Wp[3][ldp][K] (ldp = dh_debug_x6_plane_rows(ncols),
  * uint16 bit patterns), then Y = X Wt^T (+ bias on rows r % C == 0) (+ R) with
- * K % 32 == 0 and X holding round_up(rows, 256) rows; variant -1 = automatic. */
+ * K % 32 == 0 and X holding round_up(rows, 256) rows.  The codes production picks: 44, 46
+ * (gemm_x6d, 128 x 192 and 256 x 128 tiles), 52, 56, 57, 58 (gemm_x6q, 256 x 128 / 256 / 192 /
+ * 160), 76, 77 (gemm_x6m, 256 x 256 / 192), -1 = automatic.  Kept beside them for comparison:
+ * 40, 41, 43, 45, 60, 61, 62 (gemm_x6d), 50, 51 (gemm_x6q), 79 .. 83, 90 (gemm_x6m).  Any other
+ * code: DH_EINVAL, checked before any pointer is used.
+ * dh_debug_gemm_x6_choice: the code the automatic choice takes for (rows, ncols); host only. */
+int dh_debug_gemm_x6_choice(int rows, int ncols);
 int dh_debug_x6_plane_rows(int ncols);
 int dh_debug_split_planes(const float* Wt, int ldw, int ncols, int K, uint16_t* Wp, void* stream);
 int dh_debug_gemm_x6(int variant, const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias,

@@ -260,3 +260,33 @@ def test_restore_keeps_params_when_optimizer_changed(tmp_path):
     np.savez_compressed(path2, **bad)
     with pytest.raises(RuntimeError):
         LogManager.restore_checkpoint(path2, model, torch.device("cpu"), lambda params: KfacLike())
+
+
+def test_gemm_x6_choice_table():
+    """The split-bf16 dispatch (gemm_x6_choose) by shape, on both sides of the 65,536-row threshold."""
+    lib = _lib.load()
+    want = {
+        65536: {768: 76, 512: 76, 1024: 76, 192: 77, 256: 56, 2320: 56, 480: 58, 384: 57, 100: 52, 18: 52},
+        65535: {768: 44, 192: 44, 256: 46, 480: 46, 2320: 46, 18: 46},
+    }
+    for rows, by_ncols in want.items():
+        for ncols, code in by_ncols.items():
+            assert lib.dh_debug_gemm_x6_choice(rows, ncols) == code, (rows, ncols)
+
+
+def test_removed_gemm_codes_are_errors():
+    """A variant code with no kernel behind it is DH_EINVAL with a message, decided before any
+    pointer is used (null pointers here), not a launch of some other kernel."""
+    lib = _lib.load()
+    null = C.c_void_p(0)
+
+    def rejected(rc):
+        assert rc != 0
+        assert len(lib.dh_last_error()) > 0
+
+    for v in (0, 12, 86):
+        rejected(lib.dh_debug_gemm_x6(v, null, 256, null, 1024, null, null, 256, null, 256, 256, 256, 256, 1, null))
+    for v in (3, 118):
+        rejected(lib.dh_debug_gemm(v, null, 256, null, 256, null, null, 256, null, 256, 256, 256, 256, 1, null))
+    for nw in (5, 32):
+        rejected(lib.dh_debug_gemm_x6_ln(0, nw, null, 256, null, 1024, null, null, null, 768, 256, null))

@@ -1,9 +1,11 @@
 """GPU unit tests of the GEMM kernels through the C ABI test hooks, against float64 torch.
 
-Every tile variant of the register-staged GEMM (dh_debug_gemm 0..11), of the LDS-DMA
-NT GEMM (100+), and the log-psi GEMM with the LayerNorm fused into its epilogue
-(dh_debug_gemm_ln), on hot-path shapes including ragged rows / columns, the
-channel-row bias rule (bias on rows r % C == 0 only) and the residual.
+Every tile variant that is built: the register-staged GEMM (dh_debug_gemm 0..11 but 3), the
+LDS-DMA NT GEMM (100+, persistent 120+), the split-bf16 GEMM (dh_debug_gemm_x6, X6_VARIANTS
+below, and its automatic choice on both sides of the 65,536-row threshold) and the log-psi
+GEMMs with the LayerNorm fused into their epilogue
+(dh_debug_gemm_ln, dh_debug_gemm_x6_ln), on hot-path shapes including ragged rows /
+columns, the channel-row bias rule (bias on rows r % C == 0 only) and the residual.
 Tolerance: f32 products of K = 256 terms, |err| <= 2e-5 * (sum_k |x w| + 1).
 """
 
@@ -40,7 +42,7 @@ def _ref(X, W, b, R, rows, Cc):
 
 
 SHAPES = [(1000, 256, 256, 17), (24576 // 8, 768, 256, 1), (777, 192, 256, 17), (300, 100, 256, 1)]
-VARIANTS = list(range(12)) + [100 + v for v in (0, 1, 2, 3, 4, 5, 6, 7, 10, 11, 14, 15, 16, 17, 18)]
+VARIANTS = [0, 1, 2, 4, 5, 6, 7, 8, 9, 10, 11] + [100 + v for v in (0, 1, 2, 3, 4, 5, 6, 7, 10, 11, 14, 15, 16, 17)]
 PERSISTENT = [120 + v for v in range(7)]  # write padding rows / columns (Y padded to 256 x 256)
 VARIANTS += PERSISTENT
 
@@ -74,7 +76,7 @@ def test_gemm_variants(cuda, variant):
             assert torch.isnan(Y[rows:]).all()  # rows past `rows` untouched
 
 
-X6_VARIANTS = [-1, 0, 12, 40, 41, 43, 44, 45, 46, 50, 51, 52, 56, 57, 60, 61, 62, 76, 77, 78, 79, 80, 81, 82, 83, 84, 85, 90]
+X6_VARIANTS = [-1, 40, 41, 43, 44, 45, 46, 50, 51, 52, 56, 57, 58, 60, 61, 62, 76, 77, 79, 80, 81, 82, 83, 90]
 
 
 def _x6_planes(lib, W, n, K):
@@ -103,13 +105,9 @@ def test_x6_split_planes_exact(cuda):
     assert (f[1].abs() <= f[0].abs() * 2.0**-8).all() and (f[2].abs() <= f[1].abs() * 2.0**-8).all()
 
 
-@pytest.mark.parametrize("variant", X6_VARIANTS)
-def test_gemm_x6_variants(cuda, variant):
-    """Split-bf16 GEMM: correct contract (bias rule, residual, ragged rows / columns) and an
-    error vs float64 at the level of the exact-f32 MFMA kernel on the same data."""
-    lib = _lib.load()
-    g = torch.Generator(device="cpu").manual_seed(100 + variant)
-    for rows, n, K, Cc in SHAPES + [(4096, 480, 256, 1), (2048, 256, 256, 17)]:
+def _check_gemm_x6(lib, variant, shapes, seed):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    for rows, n, K, Cc in shapes:
         rp = (rows + 255) // 256 * 256
         X = torch.randn(rp, K, generator=g).cuda()
         W = (torch.randn(K, n, generator=g) / 16).cuda()
@@ -132,6 +130,21 @@ def test_gemm_x6_variants(cuda, variant):
         assert err < 2e-5, (variant, rows, n, err)
         assert err <= 2.0 * err_f32 + 1e-8, (variant, rows, n, err, err_f32)
         assert torch.isnan(Yb[rows:]).all()
+
+
+@pytest.mark.parametrize("variant", X6_VARIANTS)
+def test_gemm_x6_variants(cuda, variant):
+    """Split-bf16 GEMM: correct contract (bias rule, residual, ragged rows / columns) and an
+    error vs float64 at the level of the exact-f32 MFMA kernel on the same data."""
+    _check_gemm_x6(_lib.load(), variant, SHAPES + [(4096, 480, 256, 1), (2048, 256, 256, 17)], 100 + variant)
+
+
+@pytest.mark.parametrize("ncols", [768, 192, 256, 480])
+def test_gemm_x6_auto_channel_rows(cuda, ncols):
+    """The automatic choice on the channel-row side of the 65,536-row threshold (codes 76, 77,
+    56, 58; every -1 case above has fewer rows): a ragged last tile just over the threshold,
+    same contract and gates as test_gemm_x6_variants."""
+    _check_gemm_x6(_lib.load(), -1, [(65536 + 77, ncols, 256, 17)], 200 + ncols)
 
 
 @pytest.mark.parametrize("mode", [0, 1])

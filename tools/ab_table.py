@@ -1,4 +1,4 @@
-"""Summarise bench JSON lines (tools/ab_bench.sh, tools/runs/*.sh A/B runs): value, walker-steps/s,
+"""Summarise bench JSON lines (tools/ab_bench.sh A/B runs): value, walker-steps/s,
 C4 / C5 lines and per-kernel ms per step.  usage: ab_table.py [files...] (default gpurun_out/ab/*.json)"""
 import glob
 import json

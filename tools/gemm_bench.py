@@ -1,4 +1,7 @@
-"""GEMM kernel variants on the shapes of the C2 hot path (GPU box): TFLOP/s + correctness."""
+"""GEMM kernel variants on the shapes of the C2 hot path (GPU box): TFLOP/s + correctness.
+
+usage: gemm_bench.py [codes...]: the codes of dh_debug_gemm (include/deephall_amd.h), or
+200 + a code of dh_debug_gemm_x6 (199 = automatic choice)."""
 
 import ctypes as C
 import sys
@@ -70,12 +73,12 @@ def run(variant, rows, ncols, K, Cc, reps=20, check=False, residual=False):
 
 
 if __name__ == "__main__":
-    variants = [int(v) for v in sys.argv[1:]] or [0, 1, 2, 3, 4, 5]
+    variants = [int(v) for v in sys.argv[1:]] or [0, 1, 2, 4, 5, 9, 10]
     for name, (rows, n, k, cc) in SHAPES.items():
         line = [f"{name:8s}"]
         for v in variants:
             try:
-                ms, tf = run(v, rows, n, k, cc, check=not (290 <= v < 300 or 286 <= v <= 289), residual=name in ("el_d", "fwd_d"))
+                ms, tf = run(v, rows, n, k, cc, check=True, residual=name in ("el_d", "fwd_d"))
                 line.append(f"v{v}: {ms * 1e3:8.1f}us {tf:6.1f}TF")
             except AssertionError as e:
                 line.append(f"v{v}: WRONG {e}")

@@ -1,7 +1,7 @@
 """Run one GEMM variant on one C2 hot-path shape a few times (for rocprofv3 --pmc).
 
 variant < 200: dh_debug_gemm (>= 100: NT kernels); variant >= 200: split-bf16 kernel
-variant - 200 through dh_debug_gemm_x6 (199 = automatic choice)."""
+variant - 200 through dh_debug_gemm_x6 (199 = automatic choice).  The codes: include/deephall_amd.h."""
 import ctypes as C
 import sys
 from pathlib import Path

@@ -1,5 +1,5 @@
 # PMC counters of GEMM variants on one hot-path shape (run on the GPU box).
-# VARIANTS="106 200" SHAPE="417792 256 256" TAG=el_d bash tools/pmc_gemm.sh
+# VARIANTS="106 256" SHAPE="417792 256 256" TAG=el_d bash tools/pmc_gemm.sh
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 SHAPE=${SHAPE:-"417792 256 256"}

@@ -1,7 +1,8 @@
-"""Ring depth of the split-bf16 log-psi GEMMs (gemm_x6d_kernel ST): microseconds per launch
-and max error vs float64 on the C2 log-psi shapes (24576 rows), GPU box.
-  plain GEMM: variants 44 / 46 (ST 2) vs 70-75 (ST 4-5)
-  LayerNorm GEMM: nw 1 (96 rows, ST 3) vs 5 / 6 (ST 5 / 4), 7 (64 rows, ST 5)"""
+"""The split-bf16 log-psi GEMMs (gemm_x6d_kernel): microseconds per launch and max error vs
+float64 on the C2 log-psi shapes (24576 rows), GPU box.
+  plain GEMM: variants 44 / 46 (two buffers) and the automatic choice
+  LayerNorm GEMM: nw 1 / 2 / 8 (96 / 64 / 128 rows, three buffers)
+(The deeper rings this tool compared them with, ST 4-5, were slower: profiles/r02_ring_depth_bench.json.)"""
 
 import ctypes as C
 import json
@@ -43,7 +44,7 @@ for n in (256, 768, 192):
     assert lib.dh_debug_split_planes(p(W.t().contiguous()), K, n, K, p(Wp), s) == 0
     b = torch.randn(n, device="cuda")
     ref = (X[:rows].double() @ W.double() + b.double())
-    for v in (-1, 44, 46, 70, 71, 72, 73, 74, 75):
+    for v in (-1, 44, 46):
         Y = torch.zeros(rp, n, device="cuda")
         us = timed(lambda: lib.dh_debug_gemm_x6(v, p(X), K, p(Wp), ldn, p(b), None, n, p(Y), n, rows, n, K, 1, s))
         err = ((Y[:rows].double() - ref).abs().max() / ref.abs().max()).item()
@@ -63,7 +64,7 @@ for mode in (0, 1):
     pre = h0[:rows].double() + (z if mode == 0 else torch.tanh(z))
     mu = pre.mean(-1, keepdim=True)
     ref = (pre - mu) / torch.sqrt(((pre - mu) ** 2).mean(-1, keepdim=True) + 1e-5)
-    for nw in (1, 5, 6, 7):
+    for nw in (1, 2, 8):
         h = h0.clone()
         assert lib.dh_debug_gemm_x6_ln(mode, nw, p(Xm), K, p(Wp), ldp, p(b), p(ln), p(h), rows, K, s) == 0
         torch.cuda.synchronize()
