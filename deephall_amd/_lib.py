@@ -65,6 +65,7 @@ EXPORTS = [
     "dh_debug_split_planes",
     "dh_debug_gemm_x6",
     "dh_debug_gemm_x6_choice",
+    "dh_debug_route",
     "dh_ref_layout",
     "dh_set_params_ref",
     "dh_vjp_workspace_bytes",
@@ -186,6 +187,8 @@ def load(path: Path | str | None = None):
     lib.dh_debug_gemm_x6.restype = i32
     lib.dh_debug_gemm_x6_choice.argtypes = [i32, i32]
     lib.dh_debug_gemm_x6_choice.restype = i32
+    lib.dh_debug_route.argtypes = [vp, i32, i32, C.POINTER(i32), i32]
+    lib.dh_debug_route.restype = i32
     lib.dh_ref_layout.argtypes = [vp, C.POINTER(sz), i32]
     lib.dh_ref_layout.restype = i32
     lib.dh_set_params_ref.argtypes = [vp, vp, sz, vp]

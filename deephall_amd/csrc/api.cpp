@@ -39,11 +39,12 @@ int check_launch() {
 
 size_t align64(size_t n) { return (n + 63) / 64 * 64; }
 
-// Workspace of one pass (floats), carved from the caller's buffer.
+// Workspace of one pass (floats), carved from the caller's buffer, and the route the pass takes.
 struct Work {
   float *h, *qkv, *o, *t, *F, *geo, *x2, *logpsi, *lp;
   int32_t* nacc;
   size_t total_bytes;
+  TrunkRoute route;
 };
 
 // envelope first (det.hip): floats of S, FS, E2, Weff for nw walkers (each padded to 256 rows)
@@ -52,15 +53,17 @@ size_t env_first_floats(const Dims& d, int nw) {
   return align64(r6 * 256) + align64(r6 * d.ld_orb) + align64(r1 * env_first_k(d)) + align64(r1 * 256 * 2 * d.N);
 }
 
-Work carve(const Dims& d, int nw, int C, void* base) {
+Work carve(const Dims& d, int gemm_mode, int nw, int C, void* base) {
   const int rows = nw * d.N * C;
+  const TrunkRoute route = trunk_route(d, gemm_mode, C, rows);
   // + CH_BM rows: the channel chain's electron-aligned 96-row tiles read past the last row
   const size_t rp = (size_t)round_up(std::max(rows, 1) + 96, kWalkerRowPad);
   const size_t nh = align64(rp * d.D);
   size_t nqkv = align64(rp * (size_t)std::max(3 * d.D, d.ld_orb));
-  if (C > 1 && env_first(d))  // no F over the channel rows: S, FS, E2, Weff share the q|k|v buffer
+  if (route.det == DET_ENV_FIRST)  // no F over the channel rows: S, FS, E2, Weff share the q|k|v buffer
     nqkv = align64(std::max(rp * (size_t)(3 * d.D), env_first_floats(d, nw)));
   Work w{};
+  w.route = route;
   size_t off = 0;
   auto take = [&](size_t n) {
     float* p = base ? reinterpret_cast<float*>(base) + off : nullptr;
@@ -71,7 +74,8 @@ Work carve(const Dims& d, int nw, int C, void* base) {
   w.qkv = take(nqkv);
   w.o = take(nh);
   w.t = take(nh);
-  w.F = w.qkv;  // orbital features reuse the QKV buffer (free after the last attention)
+  // orbital features reuse the QKV buffer (free after the last attention)
+  w.F = route.orbital == ORB_NONE ? nullptr : w.qkv;
   w.geo = take((size_t)nw * d.N * 4);
   w.x2 = take((size_t)nw * d.N * 2);
   w.logpsi = take((size_t)nw * 2);
@@ -678,186 +682,170 @@ int dh_set_gemm_mode(dh_handle* h, int mode) {
 
 size_t dh_workspace_bytes(const dh_handle* h, int batch, int op) {
   if (!h || batch < 1) return 0;
-  return carve(h->d, batch, op == 1 ? h->d.C : 1, nullptr).total_bytes;
+  return carve(h->d, h->gemm_mode, batch, op == 1 ? h->d.C : 1, nullptr).total_bytes;
 }
 
 }  // extern "C"
 
 namespace {
 
-// One Psiformer pass over nw walkers with C channels; leaves orbital features in w.F.
-// geo_ready: w.geo already holds the walkers' geometry (written by the MCMC proposal); the
-// input kernel is then skipped when the geometry is all it would write.
-int run_trunk(dh_handle* h, const float* x, int nw, int C, const Work& w, hipStream_t s, bool geo_ready = false,
-              bool keep_h = false) {
-  const Dims& d = h->d;
-  const Params& P = h->p;
-  const int rows = nw * d.N * C;
-  const int D = d.D;
+// One dense GEMM Y = X W (+ bias) (+ Res) of the family: the split-bf16 planes Wp, the transposed
+// copy Wt (NT) or W itself (row stride ldw).
+void dense_gemm(int family, const float* X, int ldx, const float* W, const float* Wt, const uint16_t* Wp, int ldw,
+                const float* bias, const float* Res, int ldr, float* Y, int ldy, int rows, int ncols, int K, int C,
+                hipStream_t s) {
+  if (family == GEMM_X6)
+    launch_gemm_x6(X, ldx, Wp, x6_plane_rows(ncols), bias, Res, ldr, Y, ldy, rows, ncols, K, C, s);
+  else if (family == GEMM_F32_NT)
+    launch_gemm_nt(X, ldx, Wt, K, bias, Res, ldr, Y, ldy, rows, ncols, K, C, s);
+  else
+    launch_gemm(X, ldx, W, ldw, bias, Res, ldr, Y, ldy, rows, ncols, K, C, s);
+}
+
+// One Psiformer pass over nw walkers with C channels, walking its TrunkRoute.
+struct Trunk {
+  dh_handle* h;
+  const Dims& d;
+  const Params& P;
+  const Work& w;
+  hipStream_t s;
+  const int nw, C, rows;
+  const TrunkRoute r;
+  const bool keep_h;
+  const int D = d.D, KO = ofeat_k(d);  // KO: layer 1's o~ row length
+  const int ch = C > 1 ? PK_CH : 0;    // profiler class offset of channel-row launches
   const double R = rows, DD = D, f4 = 4.0;
-  const bool nt = P.WorbT != nullptr;
-  // channel rows (local energy) take the split-bf16 GEMM unless exact-f32 is requested;
-  // the log-psi rows only in DH_GEMM_X6_ALL, the LayerNorm-carrying GEMMs with their
-  // LayerNorm in the split-bf16 epilogue (96-row tiles of 3 x 4 waves: 34 / 38 us at
-  // 24576 x 256 x 256 against 43 / 47 us for the exact-f32 gemm_ln_kernel;
-  // tools/ln_gemm_bench.py on MI355X)
-  const bool x6 = nt && gemm_x6_supported(D) &&
-                  (C > 1 ? h->gemm_mode != DH_GEMM_F32
-                         : (h->gemm_mode == DH_GEMM_X6_ALL || h->gemm_mode == DH_GEMM_X6_ALL_UNFUSED));
-  const bool ln_fused = nt && C == 1 && gemm_ln_supported(D, D);
-  auto gemm = [&](const float* X, int ldx, const float* W, const float* Wt, const uint16_t* Wp, int ldw,
-                  const float* bias, const float* Res, int ldr, float* Y, int ldy, int ncols, int K) {
-    PROF(PK_GEMM + (C > 1 ? PK_CH : 0), 2.0 * R * ncols * K, f4 * (R * K + (double)K * ncols + R * ncols * (Res ? 2 : 1)));
-    if (x6)
-      launch_gemm_x6(X, ldx, Wp, x6_plane_rows(ncols), bias, Res, ldr, Y, ldy, rows, ncols, K, C, s);
-    else if (nt)
-      launch_gemm_nt(X, ldx, Wt, K, bias, Res, ldr, Y, ldy, rows, ncols, K, C, s);
-    else
-      launch_gemm(X, ldx, W, ldw, bias, Res, ldr, Y, ldy, rows, ncols, K, C, s);
-  };
-  // Layer-1 q|k|v come straight from the K=4 features through the folded W0 Wqkv: inside
-  // the attention kernel when it supports that (fused), else written by the input kernel.
-  const bool fold = d.L > 0;
-  const bool fused = fold && attention_takes_features(d, C);
-  const int KO = ofeat_k(d);  // layer 1's o~ row length (fused channel attention, chain prologue)
-  // log psi, split-bf16: layer 1's residual h = features W0 is formed in the epilogue of
-  // its LayerNorm GEMM from geo, so the input kernel only writes the geometry
-  const bool h_feat = C == 1 && fused && x6 && ln_fused;
-  // log psi, split-bf16, D = 256: each layer's tail (Wo Wl + LN1, Wm + LN2) and the next
-  // linear map (the next layer's q|k|v, or the orbitals) run as ONE launch (chain_x6s_kernel).
-  // Its 96-row tiles suit up to ~64K walker rows (C2 24576: 256 tiles, C4 40960: 427); at
-  // C5 (81920 rows, 2320 orbital columns) the separate GEMMs with 128-row LayerNorm tiles are
-  // faster (102.6 vs 103.6 ms per step, tools/chain_bench.py, profiles/)
-  // At N = 20 (C5) the chain is taken past 64K rows too (round 6): layer 1 with its attention in
-  // the prologue (attention, two LayerNorm GEMMs and layer 2's q|k|v in one launch), layer 2 with
-  // the 2320-column orbital map as its last pass (C5 73.5 -> 74.2 K E_L/s, 2.53 -> 2.59 M
-  // walker-steps/s same box, profiles/r06_v35_chain_big20_ab.txt)
-  const bool chain_any = C == 1 && x6 && ln_fused && D == 256;
-  auto chain_at = [&]() { return chain_any && (rows < 65536 || d.N >= 20); };
-  // local energy, split-bf16, D = 256, N <= 8: GEMM + channel LayerNorm fused per map
-  const bool lnch = C > 1 && x6 && C == 2 * d.N + 5 && h->gemm_mode != DH_GEMM_X6_ALL_UNFUSED &&
-                    gemm_lnch_supported(d.N, D);
-  // local energy, gemm_lnch: layer 1's residual h0 = f W0 is formed in the first launch's
-  // epilogue from geo
-  const bool lnch_feat = lnch && fused;  // fused: the input kernel writes no q|k|v
-  // local energy at N = 10, 20 (GEMM + layernorm_ch_quad): the same residual formed by the
-  // first LayerNorm launch, the GEMM writing t without it
-  const bool ln_feat = C > 1 && !lnch && fused && D == 256 && (d.N == 10 || d.N == 20);
-  {
-    const bool wq = fold && !fused;
-    if (!(geo_ready && h_feat && !wq)) {
-      PROF(PK_INPUT + (C > 1 ? PK_CH : 0), 8.0 * R * DD * (wq ? 4 : 1), f4 * R * DD * (wq ? 4 : 1));
-      launch_input(d, x, P.W0, wq ? P.W0qkv : nullptr, wq ? P.layer[0].bqkv : nullptr, (h_feat || lnch_feat || ln_feat) ? nullptr : w.h,
-                   wq ? w.qkv : nullptr, w.geo, nw, C, s);
-    }
+
+  void gemm(const float* X, int ldx, const float* W, const float* Wt, const uint16_t* Wp, int ldw, const float* bias,
+            const float* Res, int ldr, float* Y, int ldy, int ncols, int K) const {
+    PROF(PK_GEMM + ch, 2.0 * R * ncols * K, f4 * (R * K + (double)K * ncols + R * ncols * (Res ? 2 : 1)));
+    dense_gemm(r.family, X, ldx, W, Wt, Wp, ldw, bias, Res, ldr, Y, ldy, rows, ncols, K, C, s);
   }
-  for (int l = 0; l < d.L; ++l) {
+  X6Feat h0_feat(int l) const { return (r.h0_epilogue && l == 0) ? X6Feat{P.W0, w.geo, d.N, d.n_up} : X6Feat{}; }
+
+  // log psi: Wo Wl + LN1, Wm + LN2 and the next linear map (the next layer's q|k|v, or the
+  // orbitals) in one launch; attn: layer 1's attention in its prologue
+  void layer_chain(int l, bool attn) const {
     const LayerParams& lp = P.layer[l];
-    const bool chain = chain_at();
-    if (l > 0 && !chain_at())  // (a chained layer's last pass wrote this layer's q|k|v)
-      gemm(w.h, D, lp.Wqkv, lp.WqkvT, lp.WqkvP, 3 * D, lp.bqkv, nullptr, 0, w.qkv, 3 * D, 3 * D, D);
-    // log psi, chain form: layer 1's attention runs in the chain kernel's prologue (its o
-    // never leaves the CU; attn_val.h)
-    const bool attn_in_chain = chain && fused && l == 0 && chain_attn_supported(d.N, d.H, d.dh);
-    if (!attn_in_chain) {
-      const bool f = fused && l == 0;
-      PROF(PK_ATTN + (C > 1 ? PK_CH : 0), 0.0, f4 * R * (f ? 1.0 : 4.0) * DD);
-      launch_attention(d, w.qkv, w.geo, w.o, nw, C, s, f ? P.W0qkv : nullptr, f ? lp.bqkv : nullptr,
-                       f ? P.Mqk : nullptr);
+    const bool last = l + 1 == d.L;
+    const int n3 = last ? d.orb_cols : 3 * D;
+    PROF(PK_GEMM, 2.0 * R * DD * (2.0 * DD + n3), f4 * (2.0 * R * DD + R * n3 + 2.0 * DD * DD + DD * n3));
+    X6Feat feat = h0_feat(l);
+    if (attn) {
+      feat.W0qkv = P.W0qkv;
+      feat.bqkv = lp.bqkv;
+      feat.Mqk = P.Mqk;
+      feat.L1V = P.L1VP;
+      feat.L1B = P.L1BP;
     }
-    if (chain) {
-      const bool last = l + 1 == d.L;
-      const int n3 = last ? d.orb_cols : 3 * D;
-      PROF(PK_GEMM, 2.0 * R * DD * (2.0 * DD + n3), f4 * (2.0 * R * DD + R * n3 + 2.0 * DD * DD + DD * n3));
-      X6Feat feat{};
-      if (h_feat && l == 0) feat = X6Feat{P.W0, w.geo, d.N, d.n_up};
-      if (attn_in_chain) {
-        feat.W0qkv = P.W0qkv;
-        feat.bqkv = lp.bqkv;
-        feat.Mqk = P.Mqk;
-        feat.L1V = P.L1VP;
-        feat.L1B = P.L1BP;
-      }
-      // layer 1 with its attention in the prologue: P1 contracts the o~ planes with U (K = 32)
-      launch_chain_x6(w.o, attn_in_chain ? P.UP : lp.WolP, x6_plane_rows(D), lp.bol, lp.ln1, lp.WmP, x6_plane_rows(D),
-                      lp.bm, lp.ln2, last ? P.WorbP : P.layer[l + 1].WqkvP, x6_plane_rows(n3),
-                      last ? P.borb : P.layer[l + 1].bqkv, n3, last ? w.F : w.qkv, last ? d.ld_orb : 3 * D, w.h, rows,
-                      feat, s, /*store_h=*/!last || keep_h);  // the last layer's h is dead: only its orbitals are read
-      continue;
+    // layer 1 with its attention in the prologue: P1 contracts the o~ planes with U (K = 32)
+    launch_chain_x6(w.o, attn ? P.UP : lp.WolP, x6_plane_rows(D), lp.bol, lp.ln1, lp.WmP, x6_plane_rows(D), lp.bm,
+                    lp.ln2, last ? P.WorbP : P.layer[l + 1].WqkvP, x6_plane_rows(n3),
+                    last ? P.borb : P.layer[l + 1].bqkv, n3, last ? w.F : w.qkv, last ? d.ld_orb : 3 * D, w.h, rows,
+                    feat, s, /*store_h=*/!last || keep_h);  // the last layer's h is dead: only its orbitals are read
+  }
+  // log psi: each GEMM carries its LayerNorm in the epilogue, in place over h
+  void layer_ln_epilogue(int l) const {
+    const LayerParams& lp = P.layer[l];
+    const bool x6 = r.family == GEMM_X6;
+    {
+      PROF(PK_GEMM, 2.0 * R * DD * DD, f4 * (3.0 * R * DD + DD * DD));
+      if (x6)
+        launch_gemm_x6_ln(w.o, D, lp.WolP, x6_plane_rows(D), lp.bol, lp.ln1, w.h, rows, D, 0, 0, s, h0_feat(l));
+      else
+        launch_gemm_ln(w.o, D, lp.WolT, D, lp.bol, lp.ln1, w.h, rows, D, 0, 0, s);
     }
-    if (ln_fused) {
-      // log psi: each GEMM carries its LayerNorm in the epilogue, in place over h
-      {
-        PROF(PK_GEMM, 2.0 * R * DD * DD, f4 * (3.0 * R * DD + DD * DD));
-        if (x6)
-          launch_gemm_x6_ln(w.o, D, lp.WolP, x6_plane_rows(D), lp.bol, lp.ln1, w.h, rows, D, 0, 0, s,
-                            (h_feat && l == 0) ? X6Feat{P.W0, w.geo, d.N, d.n_up} : X6Feat{});
-        else
-          launch_gemm_ln(w.o, D, lp.WolT, D, lp.bol, lp.ln1, w.h, rows, D, 0, 0, s);
-      }
-      {
-        PROF(PK_GEMM, 2.0 * R * DD * DD, f4 * (2.0 * R * DD + DD * DD));
-        if (x6)
-          launch_gemm_x6_ln(w.h, D, lp.WmP, x6_plane_rows(D), lp.bm, lp.ln2, w.h, rows, D, 1, 0, s);
-        else
-          launch_gemm_ln(w.h, D, lp.WmT, D, lp.bm, lp.ln2, w.h, rows, D, 1, 0, s);
-      }
-      continue;
+    PROF(PK_GEMM, 2.0 * R * DD * DD, f4 * (2.0 * R * DD + DD * DD));
+    if (x6)
+      launch_gemm_x6_ln(w.h, D, lp.WmP, x6_plane_rows(D), lp.bm, lp.ln2, w.h, rows, D, 1, 0, s);
+    else
+      launch_gemm_ln(w.h, D, lp.WmT, D, lp.bm, lp.ln2, w.h, rows, D, 1, 0, s);
+  }
+  // channel rows: each linear map and its channel LayerNorm in one launch, in place over h
+  void layer_lnch(int l) const {
+    const LayerParams& lp = P.layer[l];
+    {
+      // layer 1 (fused attention): the o~ rows against U, K = ofeat_k
+      const bool of = r.ofeat && l == 0;
+      const double KK = of ? KO : DD;
+      PROF(PK_GEMM + PK_CH, 2.0 * R * DD * KK, f4 * (R * KK + 2.0 * R * DD + DD * KK));
+      launch_gemm_lnch(d.N, w.o, of ? P.UP : lp.WolP, x6_plane_rows(D), lp.bol, lp.ln1, w.geo, w.h, nw * d.N, 0, s,
+                       (r.h0_epilogue && l == 0) ? P.W0 : nullptr, d.n_up, of ? KO : D);
     }
-    if (lnch && l == 0 && fused && d.H == 4) {
-      // layer 1 whole in one launch from the o~ rows (gemm_lnch MODE 2: LN1, Wm and tanh_ch in
-      // coefficient space, the residual h1 from the same 32-deep rows, LN2)
-      PROF(PK_L1CH, 2.0 * R * DD * 3.0 * KO, f4 * (R * KO + R * DD));
-      launch_gemm_lnch(d.N, w.o, P.UP, x6_plane_rows(D), lp.bol, lp.ln2, w.geo, w.h, nw * d.N, 2, s, P.W0, d.n_up, KO,
-                       P.L1VP, P.L1BP);
-      continue;
-    }
-    if (lnch) {
-      // channel rows: each linear map and its channel LayerNorm in one launch, in place over h
-      // (gemm_lnch.hip; the GEMM output never reaches HBM)
-      {
-        // layer 1 (fused attention): the o~ rows against U, K = ofeat_k
-        const bool of = fused && l == 0;
-        const double KK = of ? KO : DD;
-        PROF(PK_GEMM + PK_CH, 2.0 * R * DD * KK, f4 * (R * KK + 2.0 * R * DD + DD * KK));
-        launch_gemm_lnch(d.N, w.o, of ? P.UP : lp.WolP, x6_plane_rows(D), lp.bol, lp.ln1, w.geo, w.h, nw * d.N, 0, s,
-                         (lnch_feat && l == 0) ? P.W0 : nullptr, d.n_up, of ? KO : D);
-      }
-      {
-        PROF(PK_GEMM + PK_CH, 2.0 * R * DD * DD, f4 * (3.0 * R * DD + DD * DD));
-        launch_gemm_lnch(d.N, w.h, lp.WmP, x6_plane_rows(D), lp.bm, lp.ln2, w.geo, w.h, nw * d.N, 1, s);
-      }
-      continue;
-    }
-    if (C > 1 && l == 0 && fused && ln_feat && P.L1VT && layer1_ch_supported(d) &&
-        h->gemm_mode != DH_GEMM_X6_ALL_UNFUSED) {  // (the unfused mode keeps the two-kernel form: tests)
-      // layer 1 at N = 10, 20 in one launch from the o~ rows (layernorm.hip layer1_ch_kernel:
-      // LN_ch1, Wm in coefficient space, tanh_ch, LN_ch2)
-      PROF(PK_L1CH, 2.0 * R * DD * (24.0 + 27.0), f4 * (R * KO + R * DD));
-      launch_layer1_ch(d, w.o, P.UT, P.L1VT, P.W0, lp.bol, lp.ln1, lp.ln2, w.geo, w.h, nw, s);
-      continue;
-    }
+    PROF(PK_GEMM + PK_CH, 2.0 * R * DD * DD, f4 * (3.0 * R * DD + DD * DD));
+    launch_gemm_lnch(d.N, w.h, lp.WmP, x6_plane_rows(D), lp.bm, lp.ln2, w.geo, w.h, nw * d.N, 1, s);
+  }
+  // channel rows: layer 1 whole in one launch from the o~ rows (gemm_lnch MODE 2)
+  void layer_lnch_whole() const {
+    const LayerParams& lp = P.layer[0];
+    PROF(PK_L1CH, 2.0 * R * DD * 3.0 * KO, f4 * (R * KO + R * DD));
+    launch_gemm_lnch(d.N, w.o, P.UP, x6_plane_rows(D), lp.bol, lp.ln2, w.geo, w.h, nw * d.N, 2, s, P.W0, d.n_up, KO,
+                     P.L1VP, P.L1BP);
+  }
+  // channel rows, N = 10, 20: layer 1 whole in one launch from the o~ rows (layer1_ch_kernel)
+  void layer_l1ch() const {
+    const LayerParams& lp = P.layer[0];
+    PROF(PK_L1CH, 2.0 * R * DD * (24.0 + 27.0), f4 * (R * KO + R * DD));
+    launch_layer1_ch(d, w.o, P.UT, P.L1VT, P.W0, lp.bol, lp.ln1, lp.ln2, w.geo, w.h, nw, s);
+  }
+  void layer_separate(int l) const {
+    const LayerParams& lp = P.layer[l];
     // t = h + o (Wo Wl) + bo Wl    (psiformer.py:44-45, two adjacent linear maps folded);
-    // layer 1 with ln_feat: t = o (Wo Wl) + bo Wl, the LayerNorm adds h0 = f W0
-    const bool lf = ln_feat && l == 0;
-    if (fused && l == 0 && C > 1)  // layer 1's o~ rows (attention_feat2_kernel) against U
+    // layer 1 with the residual in the LayerNorm: t = o (Wo Wl) + bo Wl, the LayerNorm adds h0 = f W0
+    const bool lf = r.h0_epilogue && l == 0;
+    if (r.ofeat && l == 0)  // layer 1's o~ rows against U
       gemm(w.o, KO, nullptr, P.UT, P.UP, KO, lp.bol, lf ? nullptr : w.h, D, w.t, D, D, KO);
     else
       gemm(w.o, D, lp.Wol, lp.WolT, lp.WolP, D, lp.bol, lf ? nullptr : w.h, D, w.t, D, D, D);
     {
-      PROF(PK_LN + (C > 1 ? PK_CH : 0), 0.0, f4 * R * 2.0 * DD);
+      PROF(PK_LN + ch, 0.0, f4 * R * 2.0 * DD);
       launch_layernorm(d, w.t, nullptr, lp.ln1, w.geo, w.h, nw, C, 0, s, lf ? P.W0 : nullptr);
     }
     gemm(w.h, D, lp.Wm, lp.WmT, lp.WmP, D, lp.bm, nullptr, 0, w.o, D, D, D);
-    {
-      PROF(PK_LN + (C > 1 ? PK_CH : 0), 0.0, f4 * R * 3.0 * DD);
-      launch_layernorm(d, nullptr, w.o, lp.ln2, w.geo, w.h, nw, C, 1, s);
-    }
+    PROF(PK_LN + ch, 0.0, f4 * R * 3.0 * DD);
+    launch_layernorm(d, nullptr, w.o, lp.ln2, w.geo, w.h, nw, C, 1, s);
   }
-  // (the envelope-first local energy maps only six special rows per electron, det.hip)
-  if ((d.L == 0 || !chain_at()) && !(C > 1 && env_first(d)))
-    gemm(w.h, D, P.Worb, P.WorbT, P.WorbP, d.ld_orb, P.borb, nullptr, 0, w.F, d.ld_orb, d.orb_cols, D);
-  return check_launch();
+
+  // geo_ready: w.geo already holds the walkers' geometry (written by the MCMC proposal)
+  int run(const float* x, bool geo_ready) const {
+    if (!(geo_ready && r.input_skip)) {
+      const bool wq = r.input_qkv;
+      PROF(PK_INPUT + ch, 8.0 * R * DD * (wq ? 4 : 1), f4 * R * DD * (wq ? 4 : 1));
+      launch_input(d, x, P.W0, wq ? P.W0qkv : nullptr, wq ? P.layer[0].bqkv : nullptr, r.input_h ? w.h : nullptr,
+                   wq ? w.qkv : nullptr, w.geo, nw, C, s);
+    }
+    for (int l = 0; l < d.L; ++l) {
+      const LayerParams& lp = P.layer[l];
+      const int form = l == 0 ? r.form0 : r.form1;
+      if (l > 0 && r.qkv_gemm)
+        gemm(w.h, D, lp.Wqkv, lp.WqkvT, lp.WqkvP, 3 * D, lp.bqkv, nullptr, 0, w.qkv, 3 * D, 3 * D, D);
+      if (form != LF_CHAIN_ATTN) {
+        const bool f = r.attn_feat && l == 0;
+        PROF(PK_ATTN + ch, 0.0, f4 * R * (f ? 1.0 : 4.0) * DD);
+        launch_attention(d, w.qkv, w.geo, w.o, nw, C, s, f ? P.W0qkv : nullptr, f ? lp.bqkv : nullptr,
+                         f ? P.Mqk : nullptr);
+      }
+      switch (form) {
+        case LF_CHAIN:
+        case LF_CHAIN_ATTN: layer_chain(l, form == LF_CHAIN_ATTN); break;
+        case LF_LN_EPILOGUE: layer_ln_epilogue(l); break;
+        case LF_LNCH_WHOLE: layer_lnch_whole(); break;
+        case LF_LNCH_PAIR: layer_lnch(l); break;
+        case LF_L1CH: layer_l1ch(); break;
+        default: layer_separate(l); break;
+      }
+    }
+    if (r.orbital == ORB_GEMM)
+      gemm(w.h, D, P.Worb, P.WorbT, P.WorbP, d.ld_orb, P.borb, nullptr, 0, w.F, d.ld_orb, d.orb_cols, D);
+    return check_launch();
+  }
+};
+
+// The pass w was carved for: leaves the orbital features in w.F (where the route maps them) and,
+// with keep_h, the trunk's h in w.h (the chain form skips the last layer's otherwise).
+int run_trunk(dh_handle* h, const float* x, int nw, int C, const Work& w, hipStream_t s, bool geo_ready = false,
+              bool keep_h = false) {
+  return Trunk{h, h->d, h->p, w, s, nw, C, nw * h->d.N * C, w.route, keep_h}.run(x, geo_ready);
 }
 
 int ensure_expo(dh_handle* h) {
@@ -902,7 +890,7 @@ int dh_logpsi(dh_handle* h, const float* x, int B, float* logpsi, void* ws, size
   if (int rc = check_common(h, x, B, ws, ws_bytes, need)) return rc;
   if (!logpsi) return fail(DH_EINVAL, "null output");
   hipStream_t s = (hipStream_t)stream;
-  Work w = carve(h->d, B, 1, ws);
+  Work w = carve(h->d, h->gemm_mode, B, 1, ws);
   return value_pass(h, x, B, w, logpsi, s);
 }
 
@@ -914,7 +902,7 @@ int dh_mcmc_step(dh_handle* h, float* x, float* lp, int32_t* n_accept, int B, in
   if (!lp || !n_accept || steps < 0) return fail(DH_EINVAL, "bad MCMC arguments");
   hipStream_t s = (hipStream_t)stream;
   const Dims& d = h->d;
-  Work w = carve(d, B, 1, ws);
+  Work w = carve(d, h->gemm_mode, B, 1, ws);
   // initial log-probability (mcmc.py:142)
   if (int rc = value_pass(h, x, B, w, w.logpsi, s)) return rc;
   launch_lp_from_logpsi(w.logpsi, lp, n_accept, B, s);
@@ -982,10 +970,10 @@ int dh_local_energy(dh_handle* h, const float* x, int B, float* e_l, float* obs,
   hipStream_t s = (hipStream_t)stream;
   for (int b0 = 0; b0 < B; b0 += chunk) {
     const int nw = std::min(chunk, B - b0);
-    Work w = carve(d, nw, d.C, ws);
+    Work w = carve(d, h->gemm_mode, nw, d.C, ws);
     const float* xc = x + (size_t)b0 * d.N * 2;
     if (int rc = run_trunk(h, xc, nw, d.C, w, s)) return rc;
-    if (env_first(d)) {
+    if (w.route.det == DET_ENV_FIRST) {
       // envelope first (det.hip): PhiC straight from h, then the determinant algebra
       const size_t ne = (size_t)nw * d.N, r6 = (size_t)round_up((int)(6 * ne), 256);
       const size_t r1 = (size_t)round_up((int)ne, 256);
@@ -998,7 +986,7 @@ int dh_local_energy(dh_handle* h, const float* x, int B, float* e_l, float* obs,
                                   2.0 * ne * d.C * 256 * 2 * d.N,
              4.0 * ne * (7.0 * 256 + 6.0 * d.ld_orb + env_first_k(d) + 2.0 * 256 * 2 * d.N + d.C * 256));
         launch_env_first(d, w.h, w.geo, xc, h->norm, h->p.WorbT, h->p.borb, h->p.WorbP, h->p.W2T, h->p.W2P,
-                         h->gemm_mode != DH_GEMM_F32, nw, S, FS, E2, Weff, w.o, s);
+                         w.route.family == GEMM_X6, nw, S, FS, E2, Weff, w.o, s);
       }
       {
         PROF(PK_DET_ENERGY, 0.0, 8.0 * nw * d.C * d.N * d.N);
@@ -1011,7 +999,7 @@ int dh_local_energy(dh_handle* h, const float* x, int B, float* e_l, float* obs,
       PROF(PK_DET_ENERGY, 0.0, 4.0 * nw * d.N * d.C * d.ld_orb);
       // the trunk's o buffer (rows x D floats) is free here and holds nw K C N N complex when 2 K N <= D
       launch_det_energy(d, w.F, xc, w.geo, h->p.jastrow, h->norm, e_l + 2 * (size_t)b0, obs + 8 * (size_t)b0, nw, s,
-                        det_precontract(d) ? w.o : nullptr);
+                        w.route.det == DET_PRECONTRACT ? w.o : nullptr);
     }
     if (int rc = check_launch()) return rc;
   }
@@ -1106,36 +1094,22 @@ void vjp_forward(dh_handle* h, const float* x, int nw, float* logpsi, const Grad
   const Dims& d = h->d;
   const Params& P = h->p;
   const int rows = nw * d.N, D = d.D;
-  const bool x6 = d.D % 32 == 0 && gemm_x6_supported(D);
+  const int family = gemm_family(d, /*want_x6=*/true);  // whatever the handle's GEMM mode
   auto fwd = [&](const float* X, const float* W, const float* Wt, const uint16_t* Wp, int ncols, const float* bias,
-                 const float* Rr, float* Y) {
-    if (x6)
-      launch_gemm_x6(X, D, Wp, x6_plane_rows(ncols), bias, Rr, ncols, Y, ncols, rows, ncols, D, 1, s);
-    else if (Wt)
-      launch_gemm_nt(X, D, Wt, D, bias, Rr, ncols, Y, ncols, rows, ncols, D, 1, s);
-    else
-      launch_gemm(X, D, W, ncols, bias, Rr, ncols, Y, ncols, rows, ncols, D, 1, s);
+                 const float* Rr, float* Y, int ldy) {
+    dense_gemm(family, X, D, W, Wt, Wp, ldy, bias, Rr, Rr ? ncols : 0, Y, ldy, rows, ncols, D, 1, s);
   };
   launch_input(d, x, P.W0, nullptr, nullptr, w.hs[0], nullptr, w.geo, nw, 1, s);
   for (int l = 0; l < d.L; ++l) {
     const LayerParams& lp = P.layer[l];
-    fwd(w.hs[l], lp.Wqkv, lp.WqkvT, lp.WqkvP, 3 * D, lp.bqkv, nullptr, w.qkv[l]);
+    fwd(w.hs[l], lp.Wqkv, lp.WqkvT, lp.WqkvP, 3 * D, lp.bqkv, nullptr, w.qkv[l], 3 * D);
     launch_attention(d, w.qkv[l], w.geo, w.o[l], nw, 1, s);
-    fwd(w.o[l], lp.Wol, lp.WolT, lp.WolP, D, lp.bol, w.hs[l], w.t[l]);
+    fwd(w.o[l], lp.Wol, lp.WolT, lp.WolP, D, lp.bol, w.hs[l], w.t[l], D);
     launch_ln_fwd(w.t[l], nullptr, lp.ln1, w.h1[l], rows, D, s);
-    fwd(w.h1[l], lp.Wm, lp.WmT, lp.WmP, D, lp.bm, nullptr, w.z[l]);
+    fwd(w.h1[l], lp.Wm, lp.WmT, lp.WmP, D, lp.bm, nullptr, w.z[l], D);
     launch_ln_fwd(w.h1[l], w.z[l], lp.ln2, w.hs[l + 1], rows, D, s);
   }
-  {
-    const float* hL = w.hs[d.L];
-    if (x6)
-      launch_gemm_x6(hL, D, P.WorbP, x6_plane_rows(d.orb_cols), P.borb, nullptr, 0, w.F, d.ld_orb, rows, d.orb_cols,
-                     D, 1, s);
-    else if (P.WorbT)
-      launch_gemm_nt(hL, D, P.WorbT, D, P.borb, nullptr, 0, w.F, d.ld_orb, rows, d.orb_cols, D, 1, s);
-    else
-      launch_gemm(hL, D, P.Worb, d.ld_orb, P.borb, nullptr, 0, w.F, d.ld_orb, rows, d.orb_cols, D, 1, s);
-  }
+  fwd(w.hs[d.L], P.Worb, P.WorbT, P.WorbP, d.orb_cols, P.borb, nullptr, w.F, d.ld_orb);
   launch_det_value(d, w.F, x, P.jastrow, h->norm, logpsi ? logpsi : w.logpsi, nw, s);
 }
 
@@ -1670,11 +1644,14 @@ int dh_loss_diff(dh_handle* h, const float* e_l, const float* obs, int B, const 
 // Debug hook (tests only): run input + trunk + orbital GEMM for B walkers with
 // C = 1 (op 0) or 2N+5 (op 1) channels and leave the results in the workspace:
 // final trunk activations at float offset 0 ([rows][D]) and orbital features at
-// float offset dh_debug_offsets()[1] ([rows][ld_orb]).
+// float offset dh_debug_f_offset ([rows][ld_orb]).  Refused where the route maps no F.
 int dh_debug_trunk(dh_handle* h, const float* x, int B, int op, void* ws, size_t ws_bytes, void* stream) {
   const size_t need = h ? dh_workspace_bytes(h, B, op) : 0;
   if (int rc = check_common(h, x, B, ws, ws_bytes, need)) return rc;
-  Work w = carve(h->d, B, op == 1 ? h->d.C : 1, ws);
+  Work w = carve(h->d, h->gemm_mode, B, op == 1 ? h->d.C : 1, ws);
+  if (!w.F)
+    return fail(DH_EINVAL, "dh_debug_trunk: this config's local energy goes envelope first and maps no orbital "
+                           "features F over the channel rows");
   // keep_h: the chain form writes the last layer's h too (the production path skips it)
   return run_trunk(h, x, B, op == 1 ? h->d.C : 1, w, (hipStream_t)stream, false, /*keep_h=*/true);
 }
@@ -1686,7 +1663,9 @@ int dh_debug_env_leaf(const float* thph, int n, int M, int sq, float* out, void*
 }
 
 size_t dh_debug_f_offset(const dh_handle* h, int B, int op) {
-  Work w = carve(h->d, B, op == 1 ? h->d.C : 1, reinterpret_cast<void*>(size_t(64)));
+  if (!h || B < 1) return (size_t)-1;
+  Work w = carve(h->d, h->gemm_mode, B, op == 1 ? h->d.C : 1, reinterpret_cast<void*>(size_t(64)));
+  if (!w.F) return (size_t)-1;  // no F on this route (dh_debug_trunk refuses it too)
   return (size_t)(w.F - reinterpret_cast<float*>(size_t(64)));
 }
 
@@ -1709,6 +1688,14 @@ int dh_debug_gemm(int variant, const float* X, int ldx, const float* W, int ldw,
 }
 
 int dh_debug_gemm_x6_choice(int rows, int ncols) { return gemm_x6_choose(rows, ncols); }
+
+int dh_debug_route(const dh_handle* h, int B, int op, int* out, int n) {
+  if (!h || h->laughlin || B < 1 || (n > 0 && !out)) return fail(DH_EINVAL, "bad route query");
+  const int C = op == 1 ? h->d.C : 1;
+  const TrunkRoute r = trunk_route(h->d, h->gemm_mode, C, B * h->d.N * C);
+  if (n > 0) std::memcpy(out, &r, sizeof(int) * std::min(n, kTrunkRouteFields));
+  return kTrunkRouteFields;
+}
 
 int dh_debug_x6_plane_rows(int ncols) { return x6_plane_rows(ncols); }
 

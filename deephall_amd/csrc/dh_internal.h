@@ -71,6 +71,44 @@ struct Pass {
   int rows_pad;
 };
 
+// Which launches make up one Psiformer pass (DESIGN.md §1 "Routes"): decided once per pass by
+// trunk_route (trunk_route.cpp; host only: no device call, no allocation), then walked by
+// run_trunk, carve, dh_local_energy and the debug hooks (api.cpp).  dh_debug_route writes the
+// fields as ints in the order they stand here.
+enum GemmFamily : int { GEMM_F32_NN = 0, GEMM_F32_NT = 1, GEMM_X6 = 2 };  // exact f32 (W / W^T) or split-bf16
+enum LayerForm : int {
+  LF_SEPARATE = 0,  // GEMM, LayerNorm, GEMM, LayerNorm: four launches
+  LF_LN_EPILOGUE,   // log psi: two GEMMs with the LayerNorm in their epilogue (gemm_x6_ln / gemm_ln by family)
+  LF_CHAIN,         // log psi: launch_chain_x6, the two LayerNorm GEMMs and the next linear map in one launch
+  LF_CHAIN_ATTN,    // the same with layer 1's attention in its prologue
+  LF_LNCH_PAIR,     // channel rows: gemm_lnch, GEMM + channel LayerNorm per map (two launches)
+  LF_LNCH_WHOLE,    // channel rows: gemm_lnch MODE 2, layer 1 whole in one launch
+  LF_L1CH,          // channel rows, N = 10, 20: layer1_ch_kernel, layer 1 whole in one launch
+};
+enum OrbitalMap : int { ORB_NONE = 0, ORB_GEMM = 1, ORB_IN_CHAIN = 2 };  // none: envelope first maps no F
+// (C = 1: the value kernel) / the channel determinants straight from F / from PhiC contracted out
+// of F into w.o (det_precontract) / from PhiC formed from h without F (env_first)
+enum DetStage : int { DET_VALUE = 0, DET_DIRECT = 1, DET_PRECONTRACT = 2, DET_ENV_FIRST = 3 };
+struct TrunkRoute {
+  int family;        // GemmFamily of every dense GEMM of the pass
+  int input_h;       // the input kernel writes h0 = f W0 (else layer 1 forms it: h0_epilogue)
+  int input_qkv;     // ... and layer 1's q|k|v = f (W0 Wqkv)
+  int input_skip;    // geo is all it writes: skipped when the caller's geometry is in place
+  int form0, form1;  // LayerForm of layer 1 and of every later layer
+  int attn_feat;     // layer 1's attention forms q|k|v from the features (else reads the input kernel's)
+  int h0_epilogue;   // layer 1's residual h0 = f W0 is formed from geo in the first map's epilogue / LayerNorm
+  int ofeat;         // layer 1's first map contracts the o~ rows with U at K = ofeat_k (else o with Wol at K = D)
+  int qkv_gemm;      // layers >= 2: a q|k|v GEMM precedes attention (a chained layer's last pass wrote it already)
+  int orbital;       // OrbitalMap
+  int det;           // DetStage
+};
+constexpr int kTrunkRouteFields = 12;
+static_assert(sizeof(TrunkRoute) == kTrunkRouteFields * sizeof(int), "dh_debug_route copies the fields as ints");
+// The family a dense GEMM of this network takes: split-bf16 if wanted and D allows it, else exact f32
+int gemm_family(const Dims& d, bool want_x6);
+// gemm_mode: DH_GEMM_*; C = 1 or 2N + 5; rows = walkers * N * C
+TrunkRoute trunk_route(const Dims& d, int gemm_mode, int C, int rows);
+
 constexpr int kRowPad = 256;
 // walker-row buffers (h, qkv, o, t) are padded to 768 = lcm(96, 256) rows, so the log-psi
 // LayerNorm GEMM may take 64-, 96- or 128-row tiles without reading past the buffer

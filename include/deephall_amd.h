@@ -321,9 +321,13 @@ int dh_kinetic_from_derivatives(const double* x, const double* grad, const doubl
 int dh_profile_enable(dh_handle* h, int on);
 int dh_profile_read(dh_handle* h, double* out, int reset);
 
-/* Test hooks: run the network trunk + orbital GEMM only and leave the
+/* Test hooks: run the network trunk + orbital map only and leave the
  * activations in the workspace (trunk output at float offset 0, orbital
- * features at float offset dh_debug_f_offset). */
+ * features F [rows][ld_orb] at float offset dh_debug_f_offset).
+ * Where the pass maps no F over its rows (dh_debug_route field 10 = 0: op 1 of the
+ * envelope-first configs, one determinant of one spin block at N = 10, 20), nothing is run:
+ * dh_debug_trunk returns DH_EINVAL and dh_debug_f_offset returns (size_t)-1, as it does for a
+ * null handle or B < 1. */
 int dh_debug_trunk(dh_handle* h, const float* x, int B, int op, void* ws, size_t ws_bytes, void* stream);
 size_t dh_debug_f_offset(const dh_handle* h, int B, int op);
 /* Test hook: the envelope leaves of det.hip's env_leaf (e0, d/dtheta, d/dphi / sin theta,
@@ -379,6 +383,24 @@ int dh_debug_gemm_lnch(int N, int mode, const float* X, const uint16_t* Wp, int 
  * code: DH_EINVAL, checked before any pointer is used.
  * dh_debug_gemm_x6_choice: the code the automatic choice takes for (rows, ncols); host only. */
 int dh_debug_gemm_x6_choice(int rows, int ncols);
+/* Test hook: which launches make up one pass of B walkers (op 0: log psi, 1 channel; op 1: the
+ * local energy, 2N+5 channels, one chunk) in the handle's GEMM mode (dh_set_gemm_mode; no
+ * parameters needed).  Host only: no device call.  Writes min(n, 12) ints to out and returns 12:
+ *   0 dense GEMM family: 0 exact-f32 W, 1 exact-f32 W^T (NT), 2 split-bf16
+ *   1 the input kernel writes h0 = f W0     2 ... and layer 1's q|k|v     3 it writes the geometry
+ *     only, and is skipped when the MCMC proposal already wrote that
+ *   4 form of layer 1, 5 of every later layer: 0 GEMM, LayerNorm, GEMM, LayerNorm; 1 two GEMMs
+ *     with the LayerNorm in the epilogue; 2 chain (both and the next linear map in one launch);
+ *     3 chain with layer 1's attention in its prologue; 4 gemm_lnch pair (channel rows, GEMM +
+ *     LayerNorm per launch); 5 gemm_lnch whole layer; 6 layer1_ch (whole layer, N = 10, 20)
+ *   6 layer 1's attention forms q|k|v from the features     7 layer 1's residual h0 is formed in
+ *     its first map's epilogue / LayerNorm     8 that map contracts the o~ rows with U (K = 32)
+ *   9 layers >= 2: a q|k|v GEMM precedes attention (a chained layer's last pass wrote it)
+ *  10 orbital map: 0 none (envelope first), 1 a GEMM, 2 the last chain launch
+ *  11 determinant stage: 0 value kernel (op 0), 1 direct from F, 2 precontracted PhiC,
+ *     3 envelope first (PhiC from h, no F)
+ * DH_EINVAL (negative) for a Laughlin handle or B < 1. */
+int dh_debug_route(const dh_handle* h, int B, int op, int* out, int n);
 int dh_debug_x6_plane_rows(int ncols);
 int dh_debug_split_planes(const float* Wt, int ldw, int ncols, int K, uint16_t* Wp, void* stream);
 int dh_debug_gemm_x6(int variant, const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias,

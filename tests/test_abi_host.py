@@ -290,3 +290,71 @@ def test_removed_gemm_codes_are_errors():
         rejected(lib.dh_debug_gemm(v, null, 256, null, 256, null, null, 256, null, 256, 256, 256, 256, 1, null))
     for nw in (5, 32):
         rejected(lib.dh_debug_gemm_x6_ln(0, nw, null, 256, null, 1024, null, null, null, 768, 256, null))
+
+
+ROUTE_FIELDS = ("family", "input_h", "input_qkv", "input_skip", "form0", "form1", "attn_feat", "h0_epilogue",
+                "ofeat", "qkv_gemm", "orbital", "det")
+ROUTE_CONFIGS = [dict(nspins=(3, 0), flux=2), dict(nspins=(2, 2), flux=3), dict(nspins=(5, 0), flux=11),
+                 dict(nspins=(6, 0), flux=15), dict(nspins=(8, 0), flux=21), dict(nspins=(10, 0), flux=23),
+                 dict(nspins=(12, 0), flux=33), dict(nspins=(20, 0), flux=57),
+                 dict(nspins=(10, 0), flux=23, ndets=2),
+                 dict(nspins=(2, 1), flux=3, num_heads=2, heads_dim=8, ndets=2)]
+GEMM_MODES = {"f32": 0, "x6": 1, "x6all": 2, "x6all_unfused": 3}
+
+
+def route_sweep():
+    """(key, config, mode, op, B): every config in every GEMM mode, log psi on both sides of the
+    65,536-row chain threshold (rows = the last multiple of N below it, the first at or above it)
+    and the local energy at B = 8."""
+    for kw in ROUTE_CONFIGS:
+        N = sum(kw["nspins"])
+        name = "({},{})/{} {}x{} K{}".format(*kw["nspins"], kw["flux"], kw.get("num_heads", 4),
+                                            kw.get("heads_dim", 64), kw.get("ndets", 1))
+        for mode in GEMM_MODES:
+            for op, B in ((0, 65535 // N), (0, -(-65536 // N)), (1, 8)):
+                yield f"{name} {mode} op{op} B{B}", kw, mode, op, B
+
+
+def read_route(lib, h, B, op):
+    out = (C.c_int * len(ROUTE_FIELDS))()
+    assert lib.dh_debug_route(h, B, op, out, len(out)) == len(ROUTE_FIELDS), lib.dh_last_error()
+    return list(out)
+
+
+def test_trunk_route_table():
+    """trunk_route (which launches make up a pass; DESIGN.md "Routes") over the whole sweep
+    against tests/golden/trunk_routes.json, which was dumped from the parent's own boolean
+    expressions moved verbatim into trunk_route, before run_trunk was restructured to walk it.
+    No device is touched: dh_create and dh_set_gemm_mode need no parameters."""
+    import json
+
+    golden = json.loads((ROOT / "tests" / "golden" / "trunk_routes.json").read_text())
+    assert golden["fields"] == list(ROUTE_FIELDS)
+    want = golden["routes"]
+    n = 0
+    for key, kw, mode, op, B in route_sweep():
+        lib, spec, h, rc = make_handle(**kw)
+        assert rc == 0
+        assert lib.dh_set_gemm_mode(h, GEMM_MODES[mode]) == 0
+        assert read_route(lib, h, B, op) == want[key], key
+        lib.dh_destroy(h)
+        n += 1
+    assert n == 10 * 4 * 3
+    # the gemm_lnch debug form off: the C2 channel pass falls to the separate form (layer 1 with
+    # U and the LayerNorm-formed residual is N = 10, 20 only, so the input kernel writes h again)
+    lib, spec, h, rc = make_handle()
+    assert lib.dh_set_gemm_mode(h, GEMM_MODES["x6all"]) == 0
+    on = dict(zip(ROUTE_FIELDS, read_route(lib, h, 8, 1)))
+    assert (on["form0"], on["form1"]) == (5, 4)  # gemm_lnch whole layer, then pairs
+    old = lib.dh_debug_set_lnch_form(0)
+    try:
+        got = read_route(lib, h, 8, 1)
+    finally:
+        lib.dh_debug_set_lnch_form(old)
+    assert got == want["lnch_form=0 (6,0)/15 4x64 K1 x6all op1 B8"]
+    off = dict(zip(ROUTE_FIELDS, got))
+    assert (off["form0"], off["form1"]) == (0, 0) and off["input_h"] == 1 and off["h0_epilogue"] == 0
+    assert {k: v for k, v in off.items() if k not in ("form0", "form1", "input_h", "h0_epilogue")} == \
+        {k: v for k, v in on.items() if k not in ("form0", "form1", "input_h", "h0_epilogue")}
+    assert read_route(lib, h, 8, 1) == want["(6,0)/15 4x64 K1 x6all op1 B8"]  # restored
+    lib.dh_destroy(h)

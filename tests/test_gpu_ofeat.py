@@ -12,7 +12,8 @@ route, with a partial last tile), for N = 6 (C2), N = 3, the two-spin N = 4 and 
 90-row tiles of 9 whole walkers); at N = 20 (C5) every batch size runs the chain (80-row layer-1
 tiles of 4 walkers, 96-row layer-2 tiles with the orbital map), so the big batch must reproduce
 the small one; and the local energy of the o~ route against the float64 oracle lives in
-test_gpu_parity.py / test_gpu_floor.py."""
+test_gpu_parity.py / test_gpu_floor.py.  Which route a (config, mode, batch) takes: the Routes
+table of DESIGN.md §1 (csrc/trunk_route.cpp; pinned by test_abi_host.py's table test)."""
 
 from __future__ import annotations
 

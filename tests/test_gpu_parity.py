@@ -152,7 +152,10 @@ def test_engineered_known_answer_full_batch(cuda, name):
 def test_batch_composition_and_chunking_invariance(cuda, name, B):
     """Rows are independent of the batch and of the workspace chunking, bit for bit.  C5
     (round-5 verdict, weak 1b): 128 walkers in one chunk against chunks of <= 4 walkers, the
-    N = 20 path (env_stream_kernel at two workgroups per CU, det_value<MGV>)."""
+    N = 20 path: the envelope-first local energy (no F over the channel rows: env_coef_kernel,
+    the Weff GEMM, srows_kernel's six special rows S and their orbital map FS, env_phi_kernel, then det_energy on PhiC; DESIGN.md
+    §1 "Routes") and det_value<MGV> for log psi.  env_stream_kernel is not on this path (it
+    serves N = 20 only with several determinants or two spin blocks)."""
     ocfg = oracle_config(name)
     system, model = build(ocfg)
     params = to_device_params(make_params(ocfg))
@@ -365,8 +368,10 @@ def test_vmc_iteration_bitwise_repeatable(cuda, name, B):
     twice from the same walkers and key: walkers, E_L, observables and accept counts equal bit
     for bit.  A race, an early LDS read or an interleaving-dependent corruption (DESIGN 7.1,
     the two-tiles-per-CU fused tail) shows here while every small-batch comparison passes.
-    C5 at the bench's 4096 walkers runs multi-chunk (its F exceeds one default workspace) and
-    env_stream_kernel at two workgroups per CU (round-5 verdict, weak 1b)."""
+    C5 at the bench's 4096 walkers (round-5 verdict, weak 1b) runs the envelope-first local
+    energy: env_phi_kernel over the S / FS / Weff buffers that share the q|k|v space (21 GiB of
+    workspace, one chunk of the default 24 GiB since no F is mapped over the channel rows), not
+    env_stream_kernel (DESIGN.md §1 "Routes")."""
     from deephall_amd.random import PRNGKey
     from deephall_amd.train import make_vmc_iteration
 

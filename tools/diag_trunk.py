@@ -37,7 +37,9 @@ def run(name, B=3):
         nb = h.lib.dh_workspace_bytes(h.h, B, op)
         ws = h.workspace(nb)
         rc = h.lib.dh_debug_trunk(h.h, _ptr(xd), B, op, _ptr(ws), ws.numel(), _stream(xd.device))
-        assert rc == 0, h.lib.dh_last_error()
+        if rc != 0:  # e.g. op 1 at N = 10, 20: the envelope-first local energy maps no F
+            print(f"{name} op={op}: dh_debug_trunk refused ({rc}): {h.lib.dh_last_error().decode()}")
+            continue
         torch.cuda.synchronize()
         wf = ws.view(torch.float32)
         rows = B * N * Cn
