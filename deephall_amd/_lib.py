@@ -80,6 +80,9 @@ EXPORTS = [
     "dh_kfac_workspace_bytes",
     "dh_kfac_vjp",
     "dh_kfac_step",
+    "dh_ntk_workspace_bytes",
+    "dh_ntk_tile_walkers",
+    "dh_ntk",
 ]
 
 
@@ -205,6 +208,12 @@ def load(path: Path | str | None = None):
     lib.dh_kfac_vjp.restype = i32
     lib.dh_kfac_step.argtypes = [vp, vp, vp, f32, f32, vp, vp, f32, f32, f32, vp, vp, vp, sz, vp]
     lib.dh_kfac_step.restype = i32
+    lib.dh_ntk_workspace_bytes.argtypes = [vp, i32]
+    lib.dh_ntk_workspace_bytes.restype = sz
+    lib.dh_ntk_tile_walkers.argtypes = [vp]
+    lib.dh_ntk_tile_walkers.restype = i32
+    lib.dh_ntk.argtypes = [vp, vp, i32, vp, vp, vp, vp, sz, vp]
+    lib.dh_ntk.restype = i32
     lib.dh_grad_cotangent.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.dh_grad_cotangent.restype = i32
     lib.dh_adam_update.argtypes = [vp, vp, vp, vp, sz, f32, f32, f32, f32, i32, vp]

@@ -99,6 +99,7 @@ class LearningRate:
 class OptimizerName(str, enum.Enum):
     adam = "adam"
     kfac = "kfac"
+    minsr = "minsr"
     none = "none"
 
 
@@ -113,6 +114,17 @@ class OptimizerKfac:
 
 
 @dataclass
+class OptimizerMinsr:
+    """MinSR (optimizers.py make_minsr_training_step; not in the reference): the three knobs play
+    the roles of KFAC's here (optimizers.py KFAC_DAMPING, KFAC_NORM_CONSTRAINT) and start from
+    its values."""
+
+    lr: LearningRate = field(default_factory=lambda: LearningRate(rate=0.05))
+    damping: float = 1e-3
+    norm_constraint: float = 1e-3
+
+
+@dataclass
 class Optim:
     """config.py:160-165.  The default optimizer is KFAC, as in the reference
     (optimizers.py: make_kfac_training_step on the dh_kfac_* kernels)."""
@@ -121,6 +133,7 @@ class Optim:
     optimizer: Optional[OptimizerName] = OptimizerName.kfac
     adam: OptimizerAdam = field(default_factory=OptimizerAdam)
     kfac: OptimizerKfac = field(default_factory=OptimizerKfac)
+    minsr: OptimizerMinsr = field(default_factory=OptimizerMinsr)
 
 
 @dataclass

@@ -1316,6 +1316,102 @@ int run_vjp(dh_handle* h, const float* x, int nw, const float* ct, float* grad, 
   return vjp_backward(h, x, nw, ct, grad, acc, w, s);
 }
 
+// ---- the per-walker gradient Gram matrix (dh_ntk; ntk.hip)
+
+// Workspace of dh_ntk over nw walkers: the VJP's (one chunk), then the masked cotangents, one
+// LayerNorm's per-walker scale | bias tangents [nw][2 D], and one dense map's centred input
+// rows [rows][D], their offsets [rows] and mean row [D]
+struct NtkWork {
+  GradWork g;
+  float *ctm, *lnp, *xc, *arow, *mean;
+  size_t total_bytes;
+};
+
+NtkWork carve_ntk(const Dims& d, int nw, void* base) {
+  NtkWork w{};
+  w.g = carve_grad(d, nw, base);
+  size_t off = w.g.total_bytes / sizeof(float);
+  auto take = [&](size_t n) {
+    float* p = base ? reinterpret_cast<float*>(base) + off : nullptr;
+    off += align64(n);
+    return p;
+  };
+  w.ctm = take((size_t)nw * 2);
+  w.lnp = take((size_t)nw * 2 * d.D);
+  w.xc = take((size_t)nw * d.N * std::max(d.D, 4));
+  w.arow = take((size_t)nw * d.N);
+  w.mean = take((size_t)std::max(d.D, 4));
+  w.total_bytes = off * sizeof(float);
+  return w;
+}
+
+// The reverse pass of vjp_backward over the saved activations of vjp_forward with no weight
+// gradient formed: at every dense map of the REFERENCE tree (not the folded kernel layout) the
+// saved input rows and the output tangents go to launch_ntk_gram, which adds the map's
+// <dW_b, dW_b'> (+ <db_b, db_b'>) to T [nw][nw]; the LayerNorm and Jastrow parameters add
+// J J^T of their explicit per-walker tangents.  T must be zero at entry; the upper triangle of
+// tile pairs is accumulated and mirrored at the end.
+int ntk_backward(dh_handle* h, const float* x, int nw, const float* ct, float* T, const NtkWork& nt, hipStream_t s) {
+  const Dims& d = h->d;
+  const Params& P = h->p;
+  const GradWork& w = nt.g;
+  const int rows = nw * d.N, D = d.D, N = d.N;
+  const bool x6 = d.D % 32 == 0 && gemm_x6_supported(D);
+  const RefSeg RS{d.L, d.NB, d.sparse};
+  auto ref = [&](int seg) { return (const float*)h->ref + h->ref_offsets[seg]; };
+  auto bwd = [&](const float* dY, int n, const uint16_t* WB, const float* WBT, const float* Rr, float* dX) {
+    if (x6)
+      launch_gemm_x6(dY, n, WB, x6_plane_rows(D), nullptr, Rr, D, dX, D, rows, D, n, 1, s);
+    else
+      launch_gemm(dY, n, WBT, D, nullptr, Rr, D, dX, D, rows, D, n, 1, s);
+  };
+  // one dense map: input rows X [rows][kx] (augmented with a 1 when the map has a bias),
+  // output tangents dY [rows][ky]
+  // (kx <= D; the rows are centred on their batch mean first, ntk.hip "Precision")
+  auto gram = [&](const float* X, int ldx, int kx, const float* dY, int ldy, int ky, bool bias) {
+    launch_colsum_partial(X, ldx, rows, kx, w.P, s);
+    launch_reduce2d(w.P, grad_chunks(rows), (size_t)kx, kx, 1, kx, nt.mean, kx, 1.f / (float)rows, 0, s);
+    launch_ntk_centre(X, ldx, kx, nt.mean, bias, rows, nt.xc, nt.arow, s);
+    launch_ntk_gram(nt.xc, kx, kx, dY, ldy, ky, nt.arow, N, nw, T, s);
+  };
+  // explicit per-walker tangents J [nw][k]: T += J J^T
+  auto gram_rows = [&](const float* J, int k) { launch_ntk_gram(J, k, k, nullptr, 0, 0, nullptr, 1, nw, T, s); };
+  launch_det_bwd(d, w.F, x, P.jastrow, h->norm, ct, w.dF, w.jg, nw, s);
+  gram_rows(w.jg, 2);
+  // the orbital DenseGenerals: a row's dF is zero in the other spin block's columns, so the
+  // blocks' Gram products add up to the one over all orb_cols
+  // (columns rounded up to 4 for the kernel's float4 loads: det_bwd writes the padding 0)
+  gram(w.hs[d.L], D, D, w.dF, d.ld_orb, round_up(d.orb_cols, 4), true);
+  bwd(w.dF, d.ld_orb, P.WorbB, P.WorbBT, nullptr, w.dh);
+  for (int l = d.L - 1; l >= 0; --l) {
+    const LayerParams& lp = P.layer[l];
+    // LN2: per-walker scale | bias tangents (N rows per block), dU -> dA, dz
+    launch_ln_bwd_rows(w.h1[l], w.z[l], lp.ln2, w.dh, nullptr, w.dA, w.dz, nt.lnp, rows, D, N, s);
+    gram_rows(nt.lnp, 2 * D);
+    gram(w.h1[l], D, D, w.dz, D, D, true);      // Wm, bm
+    bwd(w.dz, D, lp.WmB, lp.WmBT, w.dA, w.dh);  // dh1 = dU + dz Wm^T
+    launch_ln_bwd_rows(w.t[l], nullptr, lp.ln1, w.dh, nullptr, w.dA, nullptr, nt.lnp, rows, D, N, s);
+    gram_rows(nt.lnp, 2 * D);
+    // t = h + (o Wo + bo) Wl, the kernels' folded map taken apart again (w.dO, w.dWol: scratch)
+    //   Wo, bo: input [o, 1], output tangent dT Wl^T
+    launch_transpose(ref(RS.lay(l, RWl)), D, D, D, w.dWol, D, s);
+    launch_gemm(w.dA, D, w.dWol, D, nullptr, nullptr, 0, w.dO, D, rows, D, D, 1, s);
+    gram(w.o[l], D, D, w.dO, D, D, true);
+    //   Wl (no bias): input o Wo + bo, output tangent dT
+    launch_gemm(w.o[l], D, ref(RS.lay(l, RWo)), D, ref(RS.lay(l, Rbo)), nullptr, 0, w.dO, D, rows, D, D, 1, s);
+    gram(w.dO, D, D, w.dA, D, D, false);
+    bwd(w.dA, D, lp.WolB, lp.WolBT, nullptr, w.dO);  // dO = dT Wol^T
+    launch_attn_bwd(d, w.qkv[l], w.dO, w.dqkv, nw, s);
+    gram(w.hs[l], D, D, w.dqkv, 3 * D, 3 * D, true);      // Wq | Wk | Wv and their biases
+    bwd(w.dqkv, 3 * D, lp.WqkvB, lp.WqkvBT, w.dA, w.dh);  // dh_l = dT + dqkv Wqkv^T
+  }
+  // h_0 = features W0 (no bias)
+  launch_ntk_features(d, w.geo, rows, w.dO, s);
+  gram(w.dO, 4, 4, w.dh, D, D, false);
+  launch_ntk_mirror(T, nw, s);
+  return check_launch();
+}
+
 
 // ---- KFAC (optimizers/kfac.py:195-241; oracle/kfac.py)
 
@@ -1507,6 +1603,41 @@ int dh_logpsi_vjp(dh_handle* h, const float* x, int B, const float* ct, float* g
       return rc;
   }
   return DH_OK;
+}
+
+size_t dh_ntk_workspace_bytes(const dh_handle* h, int batch) {
+  if (!h || h->laughlin || h->d.sparse || batch < 1) return 0;
+  return carve_ntk(h->d, batch, nullptr).total_bytes;
+}
+
+int dh_ntk_tile_walkers(const dh_handle* h) {
+  if (!h || h->laughlin || h->d.sparse) return 0;
+  return ntk_tile_walkers(h->d.N);
+}
+
+int dh_ntk(dh_handle* h, const float* x, int B, const float* ct, float* T, float* logpsi, void* ws, size_t ws_bytes,
+           void* stream) {
+  // every argument check comes before the first device call
+  if (!h) return fail(DH_EINVAL, "null handle");
+  if (h->laughlin) return fail(DH_EINVAL, "the Laughlin wavefunction has no parameters to differentiate");
+  if (h->d.sparse) return fail(DH_EINVAL, "dh_ntk supports orbital type \"full\" only");
+  if (!x || B < 1) return fail(DH_EINVAL, "bad walkers");
+  if (!ct || !T) return fail(DH_EINVAL, "null argument");
+  if (h->d.D > 1024 || h->d.dh > 1024) return fail(DH_EINVAL, "dh_ntk supports D <= 1024");
+  if (h->d.N > 32 || h->d.L > 16) return fail(DH_EINVAL, "dh_ntk supports N <= 32, L <= 16");
+  // one chunk only: a pair of walkers from two chunks would need both chunks' activations
+  if (!ws || ws_bytes < dh_ntk_workspace_bytes(h, B))
+    return fail(DH_ENOMEM, "workspace too small: dh_ntk takes the whole batch in one chunk");
+  if (!h->params_set) return fail(DH_ESTATE, "parameters not set");
+  if (!h->ref_set) return fail(DH_ESTATE, "dh_ntk needs parameters uploaded with dh_set_params_ref");
+  hipStream_t s = (hipStream_t)stream;
+  const NtkWork w = carve_ntk(h->d, B, ws);
+  float* lp = logpsi ? logpsi : w.g.logpsi;
+  if (hipMemsetAsync(T, 0, (size_t)B * B * sizeof(float), s) != hipSuccess)
+    return fail(DH_EHIP, "dh_ntk: clearing T failed");
+  vjp_forward(h, x, B, lp, w.g, s);
+  launch_ntk_mask_ct(lp, ct, w.ctm, B, s);
+  return ntk_backward(h, x, B, w.ctm, T, w, s);
 }
 
 int dh_kfac_layout(dh_handle* h, size_t* out, int n) {

@@ -345,6 +345,9 @@ int ln_bwd_blocks(int rows);
 void launch_ln_fwd(const float* a, const float* z, const float* ln, float* out, int rows, int D, hipStream_t s);
 void launch_ln_bwd(const float* a, const float* z, const float* ln, const float* dy, const float* dres, float* da,
                    float* dz, float* pg, int rows, int D, hipStream_t s);
+// rpb rows per block, one partial pair per block (rpb = N: per-walker partials, dh_ntk)
+void launch_ln_bwd_rows(const float* a, const float* z, const float* ln, const float* dy, const float* dres,
+                        float* da, float* dz, float* pg, int rows, int D, int rpb, hipStream_t s);
 void launch_attn_bwd(const Dims& d, const float* qkv, const float* dO, float* dqkv, int nw, hipStream_t s);
 void launch_tn_partial(const float* X, int ldx, const float* Y, int ldy, int rows, int M, int Nc, float* P,
                        hipStream_t s);
@@ -442,6 +445,22 @@ void launch_kfac_precondition(const KfacDevPlan& p, const float* grad, const flo
                               double lambda, double* buf, float* pg, size_t nref, double* info, hipStream_t s);
 void launch_kfac_update(float* params, const float* pg, size_t n, double* info, double lr, double norm_constraint,
                         hipStream_t s);
+
+// ntk.hip: the per-walker gradient Gram matrix (api.cpp dh_ntk)
+constexpr int kNtkTileRows = 128;  // rows (walkers x n) of one Gram tile
+int ntk_tile_walkers(int n);       // whole walkers of n rows per tile
+// T[b][b'] (nwalk x nwalk) += sum_{t in b, t' in b'} (X_t . X_t' + a_t + a_t') (Y_t . Y_t'), rows t
+// of walker b = b n .. b n + n - 1; a [rows] or null (0); Y == null: the second factor is 1.
+// Upper-triangle tile pairs only (launch_ntk_mirror completes T); n <= kNtkTileRows.
+void launch_ntk_gram(const float* X, int ldx, int Kx, const float* Y, int ldy, int Ky, const float* arow, int n,
+                     int nwalk, float* T, hipStream_t s);
+// U [rows][K] = X - mean (row stride K), a[r] = mean . U[r] + (mean . mean + bias) / 2, so that
+// X_t . X_t' + bias = U_t . U_t' + a_t + a_t'
+void launch_ntk_centre(const float* X, int ldx, int K, const float* mean, bool bias, int rows, float* U, float* a,
+                       hipStream_t s);
+void launch_ntk_mirror(float* T, int B, hipStream_t s);
+void launch_ntk_mask_ct(const float* logpsi, const float* ct, float* out, int B, hipStream_t s);
+void launch_ntk_features(const Dims& d, const float* geo, int rows, float* out, hipStream_t s);
 
 }  // namespace dh
 

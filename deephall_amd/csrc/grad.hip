@@ -480,8 +480,13 @@ int ln_bwd_blocks(int rows) { return (rows + kLnRowsPerBlock - 1) / kLnRowsPerBl
 
 void launch_ln_bwd(const float* a, const float* z, const float* ln, const float* dy, const float* dres, float* da,
                    float* dz, float* pg, int rows, int D, hipStream_t s) {
-  hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_bwd_blocks(rows)), dim3(256), 0, s, a, z, ln, dy, dres, da, dz, pg, rows,
-                     D, kLnRowsPerBlock);
+  launch_ln_bwd_rows(a, z, ln, dy, dres, da, dz, pg, rows, D, kLnRowsPerBlock, s);
+}
+
+void launch_ln_bwd_rows(const float* a, const float* z, const float* ln, const float* dy, const float* dres,
+                        float* da, float* dz, float* pg, int rows, int D, int rpb, hipStream_t s) {
+  hipLaunchKernelGGL(ln_bwd_kernel, dim3((rows + rpb - 1) / rpb), dim3(256), 0, s, a, z, ln, dy, dres, da, dz, pg,
+                     rows, D, rpb);
 }
 
 void launch_attn_bwd(const Dims& d, const float* qkv, const float* dO, float* dqkv, int nw, hipStream_t s) {

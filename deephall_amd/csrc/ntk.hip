@@ -1,0 +1,256 @@
+// The per-walker gradient Gram matrix (the neural tangent kernel of log psi) that MinSR solves
+// in sample space (api.cpp dh_ntk):
+//
+//   T[b][b'] = <g_b, g_b'>,  g_b = ct_b.re d Re log psi_b / dp + ct_b.im d Im log psi_b / dp
+//
+// For a dense map y = [x, 1] [W; bias] the per-walker weight gradient is dW_b = sum_{t in b}
+// x~_t dy_t^T over the walker's electron rows t, so
+//
+//   <dW_b, dW_b'> = sum_{t in b, t' in b'} (x_t . x_t' + 1) (dy_t . dy_t')
+//
+// — two row-Gram products multiplied element by element and summed over n x n blocks; the
+// B x P Jacobian is never formed.  ntk_gram_kernel does that for one map on the layout the
+// reverse pass already has (rows = walker x electron, features contiguous), exact f32 MFMA
+// (v_mfma_f32_32x32x2_f32, as tn_partial_kernel of grad.hip):
+//
+//   a workgroup owns the pair (I, J), I <= J, of walker tiles: tw walkers = tw n <= 128 rows
+//   each, walker-aligned, rows past the tile / the batch zero-padded, so no walker straddles
+//   two workgroups; it forms X_I X_J^T and dY_I dY_J^T in accumulators of the same layout
+//   (K streamed through LDS 32 columns at a time), multiplies them, sums each n x n block from
+//   LDS in a fixed order and ADDS it into its own entries of T.  Launches of successive maps
+//   are ordered by the stream: no atomics, and two calls give bit-identical T.
+//
+// Precision: the saved activations are LayerNorm outputs whose rows share a large common part
+// (x_t . x_t' is about D for every pair) while the tangents of a walker nearly cancel over its
+// rows, so the block sum would lose to the f32 rounding of X_I X_J^T what the VJP's X^T dY
+// loses to its own.  ntk_centre_kernel therefore takes the batch-mean row m out first:
+//   x_t . x_t' + bias = u_t . u_t' + a_t + a_t',  u = x - m,  a_t = m . u_t + (m . m + bias) / 2
+// and the kernel contracts the small u rows, adding a_t + a_t' in its epilogue.
+//
+// Parameters that belong to no dense map (LayerNorm scale / bias, the Jastrow alphas) come as
+// explicit per-walker Jacobian rows (n = 1, no dY): T += J J^T by the same kernel.
+// ntk_mirror_kernel copies the upper triangle onto the lower one: T is exactly symmetric.
+#include "dh_internal.h"
+#include "device_common.h"
+
+namespace dh {
+
+typedef float f32x16_n __attribute__((ext_vector_type(16)));
+
+namespace {
+
+constexpr int kNtkKB = 32;       // K columns staged per step
+constexpr int kNtkLd = 36;       // LDS row stride of a staged tile (16-B aligned float4 reads)
+
+// Four columns k .. k + 3 of row `row` (zeros where !ok or past K).  VEC: K % 4 == 0, ld % 4 == 0,
+// Z 16-byte aligned, so the four are in or out of range together and load as one float4.
+template <bool VEC>
+__device__ __forceinline__ float4 ntk_load4(const float* __restrict__ Z, int ld, int K, int row, int k, bool ok) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (!ok) return v;
+  const float* p = Z + (size_t)row * ld + k;
+  if (VEC) {
+    if (k < K) v = *reinterpret_cast<const float4*>(p);
+  } else {
+    if (k < K) v.x = p[0];
+    if (k + 1 < K) v.y = p[1];
+    if (k + 2 < K) v.z = p[2];
+    if (k + 3 < K) v.w = p[3];
+  }
+  return v;
+}
+
+// T[wi][wj] += sum_{i, j < n} (X_I X_J^T + a_i + a_j)[bi n + i][bj n + j] (Y_I Y_J^T)[bi n + i][bj n + j]
+// for the walker pairs of tile pair (I, J) = (blockIdx.y, blockIdx.x), I <= J; a [rows] per-row
+// offsets (null: 0); Y == null: the second factor is 1 (explicit Jacobian rows).
+// rows = nwalk * n; tw * n <= kNtkTileRows.  The next 32 columns of both tiles are fetched into
+// registers (8 float4 per thread) while the MFMAs of the current ones run.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ntk_gram_kernel(const float* __restrict__ X, int ldx, int Kx,
+                                                       const float* __restrict__ Y, int ldy, int Ky,
+                                                       const float* __restrict__ arow, int n, int tw, int nwalk,
+                                                       float* __restrict__ T) {
+  // staging: two [128][kNtkLd] tiles; epilogue: the [128][128] product
+  __shared__ float sm[kNtkTileRows * kNtkTileRows];
+  const int I = blockIdx.y, J = blockIdx.x;
+  if (I > J) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int l32 = lane & 31, lh = lane >> 5;
+  const int wr = (w >> 1) * 64, wc = (w & 1) * 64;
+  const int tr = tw * n, rows = nwalk * n;
+  float* sA = sm;
+  float* sB = sm + kNtkTileRows * kNtkLd;
+  const int fr = tid >> 3, fc = (tid & 7) * 4;  // this thread's staged rows fr + 32 q, columns fc .. fc + 3
+  f32x16_n g[2][2][2];  // [product][row half][column half]
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) g[p][a][b][e] = 0.f;
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const float* Z = p == 0 ? X : Y;
+    const int ld = p == 0 ? ldx : ldy, K = p == 0 ? Kx : Ky;
+    if (!Z) continue;
+    float4 fa[4], fb[4];
+    auto fetch = [&](int k0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int r = fr + 32 * q, ra = I * tr + r, rb = J * tr + r;
+        fa[q] = ntk_load4<VEC>(Z, ld, K, ra, k0 + fc, r < tr && ra < rows);
+        fb[q] = ntk_load4<VEC>(Z, ld, K, rb, k0 + fc, r < tr && rb < rows);
+      }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < K; k0 += kNtkKB) {
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        *reinterpret_cast<float4*>(sA + (fr + 32 * q) * kNtkLd + fc) = fa[q];
+        *reinterpret_cast<float4*>(sB + (fr + 32 * q) * kNtkLd + fc) = fb[q];
+      }
+      __syncthreads();
+      if (k0 + kNtkKB < K) fetch(k0 + kNtkKB);
+#pragma unroll
+      for (int kk = 0; kk < kNtkKB; kk += 8) {
+        // lane half lh holds columns kk + 4 lh .. + 3 of its row: MFMA u contracts column
+        // kk + u (lh = 0) and kk + 4 + u (lh = 1), the same pairing in A and B
+        float4 av[2], bv[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+          av[a] = *reinterpret_cast<const float4*>(sA + (wr + 32 * a + l32) * kNtkLd + kk + 4 * lh);
+          bv[a] = *reinterpret_cast<const float4*>(sB + (wc + 32 * a + l32) * kNtkLd + kk + 4 * lh);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+              const float x = u == 0 ? av[a].x : u == 1 ? av[a].y : u == 2 ? av[a].z : av[a].w;
+              const float y = u == 0 ? bv[b].x : u == 1 ? bv[b].y : u == 2 ? bv[b].z : bv[b].w;
+              g[p][a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(x, y, g[p][a][b], 0, 0, 0);
+            }
+      }
+    }
+  }
+  // product into LDS; C/D map: col = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5).
+  // Padded rows have dY = 0 (or, without Y, X = 0) and offset 0: their products are 0.
+  __syncthreads();
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int c = wc + 32 * b + l32;
+      const float ac = (arow && c < tr && J * tr + c < rows) ? arow[J * tr + c] : 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int r = wr + 32 * a + (e & 3) + 8 * (e >> 2) + 4 * lh;
+        const float ar = (arow && r < tr && I * tr + r < rows) ? arow[I * tr + r] : 0.f;
+        const float g1 = g[0][a][b][e] + (ar + ac);
+        sm[r * kNtkTileRows + c] = Y ? g1 * g[1][a][b][e] : g1;
+      }
+    }
+  __syncthreads();
+  for (int p = tid; p < tw * tw; p += 256) {
+    const int bi = p / tw, bj = p - bi * tw;
+    const int wi = I * tw + bi, wj = J * tw + bj;
+    if (wi >= nwalk || wj >= nwalk) continue;
+    float s = 0.f;
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) s += sm[(bi * n + i) * kNtkTileRows + bj * n + j];
+    T[(size_t)wi * nwalk + wj] += s;
+  }
+}
+
+// U[r][k] = X[r][k] - m[k] (row stride K) and a[r] = m . U[r] + (m . m + bias) / 2; one wave per row
+__global__ __launch_bounds__(256) void ntk_centre_kernel(const float* __restrict__ X, int ldx, int K,
+                                                         const float* __restrict__ m, float bias, int rows,
+                                                         float* __restrict__ U, float* __restrict__ a) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (r >= rows) return;
+  float mu = 0.f, mm = 0.f;
+  for (int k = lane; k < K; k += 64) {
+    const float mk = m[k], u = X[(size_t)r * ldx + k] - mk;
+    U[(size_t)r * K + k] = u;
+    mu = fmaf(mk, u, mu);
+    mm = fmaf(mk, mk, mm);
+  }
+  mu = wave_sum(mu);
+  mm = wave_sum(mm);
+  if (lane == 0) a[r] = mu + 0.5f * (mm + bias);
+}
+
+// T[j][i] = T[i][j], i < j
+__global__ __launch_bounds__(256) void ntk_mirror_kernel(float* __restrict__ T, int B) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)B * B) return;
+  const int j = (int)(idx / B), i = (int)(idx % B);
+  if (i < j) T[idx] = T[(size_t)i * B + j];
+}
+
+// out[b] = ct[b] where log psi_b is finite, else 0 (psi = 0: the walker has no tangent)
+__global__ __launch_bounds__(256) void ntk_mask_ct_kernel(const float* __restrict__ logpsi,
+                                                          const float* __restrict__ ct, float* __restrict__ out,
+                                                          int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const bool ok = isfinite(logpsi[2 * b]) && isfinite(logpsi[2 * b + 1]);
+  out[2 * b] = ok ? ct[2 * b] : 0.f;
+  out[2 * b + 1] = ok ? ct[2 * b + 1] : 0.f;
+}
+
+// the input features [cos th, sin th cos ph, sin th sin ph, s] (psiformer.py:51-60) of every
+// row from geo = (sin th, cos th, sin ph, cos ph), as w0_partial_kernel forms them
+__global__ __launch_bounds__(256) void ntk_features_kernel(const float* __restrict__ geo, int rows, int N, int n_up,
+                                                           float* __restrict__ out) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  const float4 g = *reinterpret_cast<const float4*>(geo + 4 * (size_t)r);
+  *reinterpret_cast<float4*>(out + 4 * (size_t)r) =
+      make_float4(g.y, g.x * g.w, g.x * g.z, ((r % N) < n_up) ? 1.f : -1.f);
+}
+
+}  // namespace
+
+int ntk_tile_walkers(int N) { return N >= 1 && N <= kNtkTileRows ? kNtkTileRows / N : 0; }
+
+void launch_ntk_gram(const float* X, int ldx, int Kx, const float* Y, int ldy, int Ky, const float* arow, int n,
+                     int nwalk, float* T, hipStream_t s) {
+  const int tw = ntk_tile_walkers(n);
+  if (tw < 1 || nwalk < 1) return;
+  const int nt = (nwalk + tw - 1) / tw;
+  auto vec_ok = [](const float* Z, int ld, int K) {
+    return !Z || (K % 4 == 0 && ld % 4 == 0 && reinterpret_cast<uintptr_t>(Z) % 16 == 0);
+  };
+  if (vec_ok(X, ldx, Kx) && vec_ok(Y, ldy, Ky))
+    hipLaunchKernelGGL(ntk_gram_kernel<true>, dim3(nt, nt), dim3(256), 0, s, X, ldx, Kx, Y, ldy, Ky, arow, n, tw,
+                       nwalk, T);
+  else
+    hipLaunchKernelGGL(ntk_gram_kernel<false>, dim3(nt, nt), dim3(256), 0, s, X, ldx, Kx, Y, ldy, Ky, arow, n, tw,
+                       nwalk, T);
+}
+
+void launch_ntk_centre(const float* X, int ldx, int K, const float* mean, bool bias, int rows, float* U, float* a,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(ntk_centre_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, X, ldx, K, mean, bias ? 1.f : 0.f,
+                     rows, U, a);
+}
+
+void launch_ntk_mirror(float* T, int B, hipStream_t s) {
+  const size_t n = (size_t)B * B;
+  hipLaunchKernelGGL(ntk_mirror_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, T, B);
+}
+
+void launch_ntk_mask_ct(const float* logpsi, const float* ct, float* out, int B, hipStream_t s) {
+  hipLaunchKernelGGL(ntk_mask_ct_kernel, dim3((B + 255) / 256), dim3(256), 0, s, logpsi, ct, out, B);
+}
+
+void launch_ntk_features(const Dims& d, const float* geo, int rows, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(ntk_features_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, geo, rows, d.N, d.n_up, out);
+}
+
+}  // namespace dh

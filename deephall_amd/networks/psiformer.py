@@ -433,6 +433,31 @@ class Psiformer:
                                        _stream(x.device)))
         return out
 
+    # ---- MinSR (dh_ntk)
+    def ntk_tile_walkers(self, device) -> int:
+        """dh_ntk_tile_walkers: walkers per tile of the Gram kernel (host only)."""
+        h = get_handle(self.spec, device)
+        return int(h.lib.dh_ntk_tile_walkers(h.h))
+
+    def ntk(self, params, data: torch.Tensor, ct: torch.Tensor, logpsi: torch.Tensor | None = None) -> torch.Tensor:
+        """The Gram matrix of the per-walker gradients (dh_ntk): float32 [B, B] with
+        T[b, b'] = <g_b, g_b'>, g_b = ct[b,0] dRe log psi_b/dp + ct[b,1] dIm log psi_b/dp over
+        the reference parameter tree.  Exactly symmetric and reproducible bit for bit; a walker
+        with non-finite log psi or zero ``ct`` has a zero row and column.  The whole batch is
+        one chunk (no silent chunking: the library raises if the workspace cannot hold it)."""
+        h = self.prepare(params, data.device)
+        x = self._check_walkers(data)
+        B = x.shape[0]
+        ct = ct.to(device=x.device, dtype=torch.float32).contiguous()
+        if tuple(ct.shape) != (B, 2):
+            raise ValueError(f"cotangents must be [{B}, 2]")
+        T = torch.empty(B, B, dtype=torch.float32, device=x.device)
+        need = h.lib.dh_ntk_workspace_bytes(h.h, B)
+        ws = h.workspace(max(need, 1))
+        _lib.check(h.lib.dh_ntk(h.h, _ptr(x), B, _ptr(ct), _ptr(T), _ptr(logpsi), _ptr(ws), ws.numel(),
+                                _stream(x.device)))
+        return T
+
     # ---- KFAC (optimizers/kfac.py:195-241; dh_kfac_*)
     def kfac_layout(self, device) -> dict:
         """dh_kfac_layout: statistics size, factor slots and dense blocks."""

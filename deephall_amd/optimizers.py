@@ -11,6 +11,9 @@ the flat parameter buffer (``dh_adam_update``, optax.adam semantics).  KFAC
 kernels: the Fisher statistics come out of the gradient's forward pass and share its
 all-reduce, the EMA / damped inverses / preconditioned, norm-constrained update run on the
 device with no host sync (the algorithm is restated in oracle/kfac.py).
+MinSR (not in the reference) takes the exact natural-gradient step in sample
+space: the per-walker gradient Gram matrix comes from the dh_ntk kernels, the 2B x 2B solve
+is float64 torch.linalg on the device, the update direction one more dh_logpsi_vjp.
 """
 
 from __future__ import annotations
@@ -19,9 +22,9 @@ import logging
 
 import torch
 
-from . import _lib
+from . import _lib, constants
 from .config import Config, LearningRate, OptimizerName
-from .loss import LossMode, make_loss_fn
+from .loss import LossMode, grad_cotangent, make_loss_fn
 from .networks.psiformer import ParamTree, _ptr, _stream
 from .types import CheckpointState
 
@@ -138,6 +141,99 @@ def make_kfac_training_step(cfg: Config, network):
     return init, step
 
 
+class MinsrState:
+    """MinSR keeps no curvature or momentum between steps: the step counter (the learning-rate
+    schedule's argument) is the whole state."""
+
+    def __init__(self):
+        self.step = 0
+
+    def state_dict(self):
+        return {"step": self.step}
+
+    def load_state_dict(self, d):
+        self.step = int(d["step"])
+
+
+def minsr_direction(net, params: ParamTree, data: torch.Tensor, diff: torch.Tensor, damping: float) -> ParamTree:
+    """The linear-algebra half of a MinSR step for given clipped energy differences ``diff``
+    [B, 2] float32 (re, im; NaN = walker dropped):
+
+        delta = 2 O~^T (O~ O~^T + damping I)^-1 eps~  =  (O~^T O~ + damping I)^-1 2 O~^T eps~
+
+    O~ [2B, P]: the rows d Re log psi_b / dp, then d Im log psi_b / dp, centred over the valid
+    walkers v (non-NaN diff, finite log psi; n of them) and divided by sqrt(n); eps~ =
+    [Re diff; Im diff] / sqrt(n), zero outside v.  O~ O~^T is the centred dh_ntk Gram matrix of
+    [data; data] with cotangents (1, 0) | (0, 1); the solve runs in float64 on the device; the
+    product with O~^T is dh_logpsi_vjp with the solution as cotangents."""
+    B = data.shape[0]
+    dev = data.device
+    ct = torch.zeros(2 * B, 2, dtype=torch.float32, device=dev)
+    ct[:B, 0] = 1.0
+    ct[B:, 1] = 1.0
+    lp = torch.empty(2 * B, 2, dtype=torch.float32, device=dev)
+    T = net.ntk(params, torch.cat([data, data]), ct, logpsi=lp).double()
+    diff = diff.to(device=dev, dtype=torch.float64)
+    valid = ~torch.isnan(diff).any(dim=1) & torch.isfinite(lp[:B]).all(dim=1)
+    v = valid.double()
+    n = v.sum().clamp(min=1.0)
+
+    def centre(a):  # C a over the last axis [.., B]: a - mean_v(a) on v, 0 outside
+        a = a * v
+        return a - v * (a.sum(-1, keepdim=True) / n)
+
+    T4 = centre(T.view(2, B, 2, B))                              # columns
+    T4 = centre(T4.permute(2, 3, 0, 1)).permute(2, 3, 0, 1)      # rows
+    Tbar = T4.reshape(2 * B, 2 * B) / n
+    eps = (torch.nan_to_num(diff, nan=0.0) * v[:, None]).t().reshape(2 * B) / n.sqrt()
+    A = Tbar + float(damping) * torch.eye(2 * B, dtype=torch.float64, device=dev)
+    L, info = torch.linalg.cholesky_ex(A)
+    if int(info) == 0:
+        y = torch.cholesky_solve(eps[:, None], L)[:, 0]
+    else:
+        y = torch.linalg.solve(A, eps)
+    ct2 = (2.0 * centre(y.view(2, B)) / n.sqrt()).t().contiguous().float()
+    return net.vjp(params, data, ct2)
+
+
+def make_minsr_training_step(cfg: Config, network):
+    """MinSR (Chen & Heyl 2024; Rende et al. 2024): stochastic reconfiguration solved in sample
+    space, delta = (S + damping I)^-1 g with S the centred 2B-sample Fisher matrix — exact, where
+    KFAC approximates — then KFAC's norm constraint against the ENERGY_GRAD gradient g:
+    c = min(1, sqrt(norm_constraint / (lr^2 <delta, g>))), params -= lr c delta."""
+    if constants.world_size() > 1:
+        raise NotImplementedError("MinSR on more than one rank needs an all-gather of the walkers' Gram rows "
+                                  "(pairs of walkers on different ranks); run it on a single rank")
+    loss_fn = make_loss_fn(network, cfg.system, LossMode.ENERGY_DIFF)
+    net = loss_fn.network
+    if net is None or not hasattr(net, "ntk"):
+        raise TypeError("MinSR needs a Psiformer of this library")
+    opt = cfg.optim.minsr
+
+    def init(params, key=None, data=None):
+        del params, key, data
+        return MinsrState()
+
+    def step(state: CheckpointState, key=None, **stat_kw):
+        params, data, opt_state, width = state
+        stats, diff = loss_fn(params, data, **stat_kw)
+        diff = torch.view_as_real(diff).contiguous()
+        nvalid = (~torch.isnan(diff).any(dim=1)).sum().float().view(1)
+        grad = net.vjp(params, data, grad_cotangent(diff, nvalid, 0))
+        delta = minsr_direction(net, params, data, diff, opt.damping)
+        lr = lr_schedule(opt.lr, opt_state.step)
+        d = torch.nan_to_num(delta.flat, nan=0.0, posinf=0.0, neginf=0.0)
+        sq = (lr * lr) * torch.dot(d.double(), torch.nan_to_num(grad.flat).double())
+        c = torch.where(sq > opt.norm_constraint, torch.sqrt(opt.norm_constraint / sq.clamp(min=1e-300)),
+                        torch.ones_like(sq))
+        params.flat.sub_((lr * c).float() * d)
+        opt_state.step += 1
+        net.invalidate()
+        return CheckpointState(params, data, opt_state, width), stats
+
+    return init, step
+
+
 def make_inference_step(cfg: Config, network):
     loss_fn = make_loss_fn(network, cfg.system, LossMode.ENERGY_DIFF)
 
@@ -161,4 +257,6 @@ def make_optimizer_step(cfg: Config, network):
         return make_inference_step(cfg, network)
     if name == OptimizerName.kfac:
         return make_kfac_training_step(cfg, network)
+    if name == OptimizerName.minsr:
+        return make_minsr_training_step(cfg, network)
     raise ValueError(f"Optimizer {name} is not implemented!")

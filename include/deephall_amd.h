@@ -171,6 +171,31 @@ int dh_kfac_step(dh_handle* h, float* raw, const float* stats, float ema, float 
                  float* params, float lr, float damping, float norm_constraint, float* pgrad, double* info, void* ws,
                  size_t ws_bytes, void* stream);
 
+/* MinSR — stochastic reconfiguration solved in sample space (B x B instead of P x P):
+ *   delta = O~^T (O~ O~^T + lambda I)^-1 eps~.   The library supplies the Gram matrix O O^T of the
+ * per-walker gradients; the centring, the solve and the update are the caller's (optimizers.py),
+ * and O~^T y is dh_logpsi_vjp with y as cotangents.  Psiformer, orbital "full", N <= 32 only.
+ *
+ * dh_ntk: with g_b = ct[b][0] d Re log psi_b / dp + ct[b][1] d Im log psi_b / dp over the
+ *   dh_ref_layout parameters (the reference tree: Wo, bo and Wl apart, not the kernels' folded
+ *   Wo Wl), T[b][b'] = <g_b, g_b'>, float32 [B][B], WRITTEN.  x, ct, logpsi as dh_logpsi_vjp.
+ *   The B x P Jacobian is never formed: every dense map adds sum_{t in b, t' in b'}
+ *   (x_t . x_t' + 1) (dy_t . dy_t') over the walkers' electron rows (exact-f32 MFMA, ntk.hip);
+ *   the LayerNorm and Jastrow parameters add J J^T of their explicit per-walker tangents.
+ *   T is exactly symmetric (the upper triangle is computed and mirrored) and two calls give
+ *   bit-identical results (no atomics).  A walker whose log psi is not finite, or whose ct is
+ *   zero, gets an exactly zero row and column.
+ *   ONE chunk: pairs of walkers from two chunks would need both chunks' activations, so
+ *   ws_bytes < dh_ntk_workspace_bytes(h, B) is DH_ENOMEM (checked, with every other argument,
+ *   before any device call); "sparse" orbitals and Laughlin handles are DH_EINVAL.
+ * dh_ntk_tile_walkers: walkers per Gram tile (host only; tile_walkers * N <= 128 rows, a
+ *   workgroup owns one pair of tiles); 0 for a handle dh_ntk does not serve.
+ * The launches are not recorded by dh_profile_* (no kernel class is theirs). */
+size_t dh_ntk_workspace_bytes(const dh_handle* h, int batch);
+int dh_ntk_tile_walkers(const dh_handle* h);
+int dh_ntk(dh_handle* h, const float* x, int B, const float* ct, float* T, float* logpsi, void* ws, size_t ws_bytes,
+           void* stream);
+
 /* Cotangents of the gradient estimator 2 nanmean(conj(d log psi) diff) (loss.py:59-64):
  * part 0 (its real part, ENERGY_GRAD): ct = 2 (Re diff, Im diff) / n;
  * part 1 (its imaginary part, SR_F_VECTOR): ct = 2 (Im diff, -Re diff) / n;
