@@ -83,6 +83,11 @@ EXPORTS = [
     "dh_ntk_workspace_bytes",
     "dh_ntk_tile_walkers",
     "dh_ntk",
+    "dh_ntk_part",
+    "dh_ntk_mirror",
+    "dh_ntk_owner",
+    "dh_minsr_matrix_workspace_bytes",
+    "dh_minsr_matrix",
 ]
 
 
@@ -214,6 +219,16 @@ def load(path: Path | str | None = None):
     lib.dh_ntk_tile_walkers.restype = i32
     lib.dh_ntk.argtypes = [vp, vp, i32, vp, vp, vp, vp, sz, vp]
     lib.dh_ntk.restype = i32
+    lib.dh_ntk_part.argtypes = [vp, vp, i32, vp, vp, vp, vp, sz, i32, i32, vp]
+    lib.dh_ntk_part.restype = i32
+    lib.dh_ntk_mirror.argtypes = [vp, i32, vp]
+    lib.dh_ntk_mirror.restype = i32
+    lib.dh_ntk_owner.argtypes = [vp, i32, i32]
+    lib.dh_ntk_owner.restype = i32
+    lib.dh_minsr_matrix_workspace_bytes.argtypes = [i32]
+    lib.dh_minsr_matrix_workspace_bytes.restype = sz
+    lib.dh_minsr_matrix.argtypes = [vp, vp, i32, C.c_double, vp, vp, sz, vp]
+    lib.dh_minsr_matrix.restype = i32
     lib.dh_grad_cotangent.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.dh_grad_cotangent.restype = i32
     lib.dh_adam_update.argtypes = [vp, vp, vp, vp, sz, f32, f32, f32, f32, i32, vp]

@@ -117,11 +117,15 @@ class OptimizerKfac:
 class OptimizerMinsr:
     """MinSR (optimizers.py make_minsr_training_step; not in the reference): the three knobs play
     the roles of KFAC's here (optimizers.py KFAC_DAMPING, KFAC_NORM_CONSTRAINT) and start from
-    its values."""
+    its values.  ``sharded``: the Gram matrix is computed in shares across the ranks
+    (optimizers.minsr_direction_sharded); opt-in, because every rank then holds the gathered
+    batch's activations and the (2 x global batch)^2 matrices.  Without it MinSR runs on one rank
+    only."""
 
     lr: LearningRate = field(default_factory=lambda: LearningRate(rate=0.05))
     damping: float = 1e-3
     norm_constraint: float = 1e-3
+    sharded: bool = False
 
 
 @dataclass

@@ -1350,13 +1350,16 @@ NtkWork carve_ntk(const Dims& d, int nw, void* base) {
 // saved input rows and the output tangents go to launch_ntk_gram, which adds the map's
 // <dW_b, dW_b'> (+ <db_b, db_b'>) to T [nw][nw]; the LayerNorm and Jastrow parameters add
 // J J^T of their explicit per-walker tangents.  T must be zero at entry; the upper triangle of
-// tile pairs is accumulated and mirrored at the end.
-int ntk_backward(dh_handle* h, const float* x, int nw, const float* ct, float* T, const NtkWork& nt, hipStream_t s) {
+// tile pairs is accumulated, of the rows that part `part` of `nparts` owns (ntk.hip "Sharding");
+// the caller mirrors it.
+int ntk_backward(dh_handle* h, const float* x, int nw, const float* ct, float* T, const NtkWork& nt, int part,
+                 int nparts, hipStream_t s) {
   const Dims& d = h->d;
   const Params& P = h->p;
   const GradWork& w = nt.g;
   const int rows = nw * d.N, D = d.D, N = d.N;
   const bool x6 = d.D % 32 == 0 && gemm_x6_supported(D);
+  const int tw_own = ntk_tile_walkers(N);
   const RefSeg RS{d.L, d.NB, d.sparse};
   auto ref = [&](int seg) { return (const float*)h->ref + h->ref_offsets[seg]; };
   auto bwd = [&](const float* dY, int n, const uint16_t* WB, const float* WBT, const float* Rr, float* dX) {
@@ -1372,10 +1375,12 @@ int ntk_backward(dh_handle* h, const float* x, int nw, const float* ct, float* T
     launch_colsum_partial(X, ldx, rows, kx, w.P, s);
     launch_reduce2d(w.P, grad_chunks(rows), (size_t)kx, kx, 1, kx, nt.mean, kx, 1.f / (float)rows, 0, s);
     launch_ntk_centre(X, ldx, kx, nt.mean, bias, rows, nt.xc, nt.arow, s);
-    launch_ntk_gram(nt.xc, kx, kx, dY, ldy, ky, nt.arow, N, nw, T, s);
+    launch_ntk_gram(nt.xc, kx, kx, dY, ldy, ky, nt.arow, N, nw, tw_own, part, nparts, T, s);
   };
   // explicit per-walker tangents J [nw][k]: T += J J^T
-  auto gram_rows = [&](const float* J, int k) { launch_ntk_gram(J, k, k, nullptr, 0, 0, nullptr, 1, nw, T, s); };
+  auto gram_rows = [&](const float* J, int k) {
+    launch_ntk_gram(J, k, k, nullptr, 0, 0, nullptr, 1, nw, tw_own, part, nparts, T, s);
+  };
   launch_det_bwd(d, w.F, x, P.jastrow, h->norm, ct, w.dF, w.jg, nw, s);
   gram_rows(w.jg, 2);
   // the orbital DenseGenerals: a row's dF is zero in the other spin block's columns, so the
@@ -1408,7 +1413,6 @@ int ntk_backward(dh_handle* h, const float* x, int nw, const float* ct, float* T
   // h_0 = features W0 (no bias)
   launch_ntk_features(d, w.geo, rows, w.dO, s);
   gram(w.dO, 4, 4, w.dh, D, D, false);
-  launch_ntk_mirror(T, nw, s);
   return check_launch();
 }
 
@@ -1615,9 +1619,9 @@ int dh_ntk_tile_walkers(const dh_handle* h) {
   return ntk_tile_walkers(h->d.N);
 }
 
-int dh_ntk(dh_handle* h, const float* x, int B, const float* ct, float* T, float* logpsi, void* ws, size_t ws_bytes,
-           void* stream) {
-  // every argument check comes before the first device call
+// dh_ntk's and dh_ntk_part's argument checks: every one comes before the first device call
+static int ntk_check(dh_handle* h, const float* x, int B, const float* ct, float* T, void* ws, size_t ws_bytes,
+                     int part, int nparts) {
   if (!h) return fail(DH_EINVAL, "null handle");
   if (h->laughlin) return fail(DH_EINVAL, "the Laughlin wavefunction has no parameters to differentiate");
   if (h->d.sparse) return fail(DH_EINVAL, "dh_ntk supports orbital type \"full\" only");
@@ -1628,16 +1632,64 @@ int dh_ntk(dh_handle* h, const float* x, int B, const float* ct, float* T, float
   // one chunk only: a pair of walkers from two chunks would need both chunks' activations
   if (!ws || ws_bytes < dh_ntk_workspace_bytes(h, B))
     return fail(DH_ENOMEM, "workspace too small: dh_ntk takes the whole batch in one chunk");
+  if (nparts < 1 || part < 0 || part >= nparts) return fail(DH_EINVAL, "dh_ntk_part needs 0 <= part < nparts");
   if (!h->params_set) return fail(DH_ESTATE, "parameters not set");
   if (!h->ref_set) return fail(DH_ESTATE, "dh_ntk needs parameters uploaded with dh_set_params_ref");
-  hipStream_t s = (hipStream_t)stream;
+  return DH_OK;
+}
+
+// the upper triangle of T, the rows of part `part` of `nparts` (everything else 0), not mirrored
+static int ntk_run(dh_handle* h, const float* x, int B, const float* ct, float* T, float* logpsi, void* ws, int part,
+                   int nparts, hipStream_t s) {
   const NtkWork w = carve_ntk(h->d, B, ws);
   float* lp = logpsi ? logpsi : w.g.logpsi;
   if (hipMemsetAsync(T, 0, (size_t)B * B * sizeof(float), s) != hipSuccess)
     return fail(DH_EHIP, "dh_ntk: clearing T failed");
   vjp_forward(h, x, B, lp, w.g, s);
   launch_ntk_mask_ct(lp, ct, w.ctm, B, s);
-  return ntk_backward(h, x, B, w.ctm, T, w, s);
+  return ntk_backward(h, x, B, w.ctm, T, w, part, nparts, s);
+}
+
+int dh_ntk(dh_handle* h, const float* x, int B, const float* ct, float* T, float* logpsi, void* ws, size_t ws_bytes,
+           void* stream) {
+  if (int rc = ntk_check(h, x, B, ct, T, ws, ws_bytes, 0, 1)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = ntk_run(h, x, B, ct, T, logpsi, ws, 0, 1, s)) return rc;
+  launch_ntk_mirror(T, B, s);
+  return check_launch();
+}
+
+int dh_ntk_part(dh_handle* h, const float* x, int B, const float* ct, float* T, float* logpsi, void* ws,
+                size_t ws_bytes, int part, int nparts, void* stream) {
+  if (int rc = ntk_check(h, x, B, ct, T, ws, ws_bytes, part, nparts)) return rc;
+  return ntk_run(h, x, B, ct, T, logpsi, ws, part, nparts, (hipStream_t)stream);
+}
+
+int dh_ntk_mirror(float* T, int B, void* stream) {
+  if (!T || B < 1) return fail(DH_EINVAL, "dh_ntk_mirror: null T or B < 1");
+  launch_ntk_mirror(T, B, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_ntk_owner(const dh_handle* h, int walker, int nparts) {
+  const int tw = dh_ntk_tile_walkers(h);
+  if (tw < 1 || h->d.N > 32 || walker < 0 || nparts < 1) return -1;
+  return (walker / tw) % nparts;
+}
+
+size_t dh_minsr_matrix_workspace_bytes(int Bg) {
+  return Bg < 1 ? 0 : minsr_matrix_ws_doubles(Bg) * sizeof(double);
+}
+
+int dh_minsr_matrix(const float* T, const unsigned char* valid, int Bg, double damping, double* A, void* ws,
+                    size_t ws_bytes, void* stream) {
+  if (!T || !valid || !A) return fail(DH_EINVAL, "dh_minsr_matrix: null argument");
+  if (Bg < 1 || Bg > (1 << 29)) return fail(DH_EINVAL, "dh_minsr_matrix: bad walker count");
+  if (!ws || ws_bytes < dh_minsr_matrix_workspace_bytes(Bg))
+    return fail(DH_ENOMEM, "dh_minsr_matrix: workspace too small");
+  if (reinterpret_cast<uintptr_t>(ws) % 8 != 0) return fail(DH_EINVAL, "dh_minsr_matrix: workspace not 8-byte aligned");
+  launch_minsr_matrix(T, valid, Bg, damping, A, reinterpret_cast<double*>(ws), (hipStream_t)stream);
+  return check_launch();
 }
 
 int dh_kfac_layout(dh_handle* h, size_t* out, int n) {

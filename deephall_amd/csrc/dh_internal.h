@@ -452,8 +452,10 @@ int ntk_tile_walkers(int n);       // whole walkers of n rows per tile
 // T[b][b'] (nwalk x nwalk) += sum_{t in b, t' in b'} (X_t . X_t' + a_t + a_t') (Y_t . Y_t'), rows t
 // of walker b = b n .. b n + n - 1; a [rows] or null (0); Y == null: the second factor is 1.
 // Upper-triangle tile pairs only (launch_ntk_mirror completes T); n <= kNtkTileRows.
+// Only rows wi of T with (wi / tw_own) % nparts == part are added to (dh_ntk_part's ownership
+// rule; tw_own = the dense maps' tile walkers; 0 of 1: every row).
 void launch_ntk_gram(const float* X, int ldx, int Kx, const float* Y, int ldy, int Ky, const float* arow, int n,
-                     int nwalk, float* T, hipStream_t s);
+                     int nwalk, int tw_own, int part, int nparts, float* T, hipStream_t s);
 // U [rows][K] = X - mean (row stride K), a[r] = mean . U[r] + (mean . mean + bias) / 2, so that
 // X_t . X_t' + bias = U_t . U_t' + a_t + a_t'
 void launch_ntk_centre(const float* X, int ldx, int K, const float* mean, bool bias, int rows, float* U, float* a,
@@ -461,6 +463,11 @@ void launch_ntk_centre(const float* X, int ldx, int K, const float* mean, bool b
 void launch_ntk_mirror(float* T, int B, hipStream_t s);
 void launch_ntk_mask_ct(const float* logpsi, const float* ct, float* out, int B, hipStream_t s);
 void launch_ntk_features(const Dims& d, const float* geo, int rows, float* out, hipStream_t s);
+// dh_minsr_matrix: A [2 Bg][2 Bg] float64 = C T C / n + damping I from the symmetric float32 T
+// and the walkers' valid flags; ws: minsr_matrix_ws_doubles(Bg) doubles
+size_t minsr_matrix_ws_doubles(int Bg);
+void launch_minsr_matrix(const float* T, const unsigned char* valid, int Bg, double damping, double* A, double* ws,
+                         hipStream_t s);
 
 }  // namespace dh
 

@@ -30,6 +30,17 @@
 // Parameters that belong to no dense map (LayerNorm scale / bias, the Jastrow alphas) come as
 // explicit per-walker Jacobian rows (n = 1, no dY): T += J J^T by the same kernel.
 // ntk_mirror_kernel copies the upper triangle onto the lower one: T is exactly symmetric.
+//
+// Sharding over ranks (dh_ntk_part): an entry T[wi][wj], wi <= wj, belongs to part
+//   owner(wi) = (wi / tw_dense) % nparts,  tw_dense = ntk_tile_walkers(N)
+// whatever the launch's own tile size, so that all of an entry's additions happen on one rank
+// in the stream's order and the sum of the parts is, bit for bit, the whole.  A dense map's
+// workgroup (tile = tw_dense walkers) leaves at once unless its tile row is the part's; a
+// per-walker-row launch (tile = 128 walkers) computes its tile and masks the final add.
+//
+// minsr_rowsum / minsr_gsum / minsr_matrix kernels (dh_minsr_matrix): the float64 matrix MinSR
+// solves, A = C T C / n + damping I with C the centring over the valid walkers, from the float32
+// T in two passes over it and one write of A.
 #include "dh_internal.h"
 #include "device_common.h"
 
@@ -62,18 +73,21 @@ __device__ __forceinline__ float4 ntk_load4(const float* __restrict__ Z, int ld,
 
 // T[wi][wj] += sum_{i, j < n} (X_I X_J^T + a_i + a_j)[bi n + i][bj n + j] (Y_I Y_J^T)[bi n + i][bj n + j]
 // for the walker pairs of tile pair (I, J) = (blockIdx.y, blockIdx.x), I <= J; a [rows] per-row
-// offsets (null: 0); Y == null: the second factor is 1 (explicit Jacobian rows).
+// offsets (null: 0); Y == null: the second factor is 1 (explicit Jacobian rows).  Only entries
+// wi <= wj of the rows with (wi / tw_own) % nparts == part are added to (header, "Sharding").
 // rows = nwalk * n; tw * n <= kNtkTileRows.  The next 32 columns of both tiles are fetched into
 // registers (8 float4 per thread) while the MFMAs of the current ones run.
 template <bool VEC>
 __global__ __launch_bounds__(256) void ntk_gram_kernel(const float* __restrict__ X, int ldx, int Kx,
                                                        const float* __restrict__ Y, int ldy, int Ky,
                                                        const float* __restrict__ arow, int n, int tw, int nwalk,
-                                                       float* __restrict__ T) {
+                                                       int tw_own, int part, int nparts, float* __restrict__ T) {
   // staging: two [128][kNtkLd] tiles; epilogue: the [128][128] product
   __shared__ float sm[kNtkTileRows * kNtkTileRows];
   const int I = blockIdx.y, J = blockIdx.x;
   if (I > J) return;
+  // tw_own: the dense maps' tile, which decides the owner of a row of T (header)
+  if (tw == tw_own && I % nparts != part) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int l32 = lane & 31, lh = lane >> 5;
   const int wr = (w >> 1) * 64, wc = (w & 1) * 64;
@@ -155,10 +169,13 @@ __global__ __launch_bounds__(256) void ntk_gram_kernel(const float* __restrict__
       }
     }
   __syncthreads();
+  // a dense map's workgroup owns all of its tile row or has left already
+  const bool masked = nparts > 1 && tw != tw_own;
   for (int p = tid; p < tw * tw; p += 256) {
     const int bi = p / tw, bj = p - bi * tw;
     const int wi = I * tw + bi, wj = J * tw + bj;
-    if (wi >= nwalk || wj >= nwalk) continue;
+    // (a diagonal tile pair's lower half is the mirror's to fill)
+    if (wi >= nwalk || wj >= nwalk || wi > wj || (masked && (wi / tw_own) % nparts != part)) continue;
     float s = 0.f;
     for (int i = 0; i < n; ++i)
       for (int j = 0; j < n; ++j) s += sm[(bi * n + i) * kNtkTileRows + bj * n + j];
@@ -214,12 +231,143 @@ __global__ __launch_bounds__(256) void ntk_features_kernel(const float* __restri
       make_float4(g.y, g.x * g.w, g.x * g.z, ((r % N) < n_up) ? 1.f : -1.f);
 }
 
+// ---- dh_minsr_matrix.  Rows (a, i), columns (c, j) of T [M][M], M = 2 Bg; halves a, c; walkers
+// i, j; v the valid flags, n = max(1, sum v).  Workspace (doubles): s [M][2], the row sums and
+// then r = s / n | g [4] | n.
+
+// sum over 256 threads' doubles in a fixed tree; the result is valid in thread 0
+__device__ __forceinline__ double minsr_block_sum(double x, double* red) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  red[tid] = x;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (tid < h) red[tid] += red[tid + h];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// pass 1: s[row][c] = sum_j v_j T[row][c Bg + j] (not yet / n); one workgroup per row, each
+// thread's columns in a fixed order, then the fixed tree
+template <bool VEC>
+__global__ __launch_bounds__(256) void minsr_rowsum_kernel(const float* __restrict__ T,
+                                                           const unsigned char* __restrict__ valid, int Bg,
+                                                           double* __restrict__ s) {
+  __shared__ double red[256];
+  const int M = 2 * Bg, row = blockIdx.x, tid = threadIdx.x;
+  const float* Tr = T + (size_t)row * M;
+  double acc[2] = {0.0, 0.0};
+  if (VEC) {
+    for (int j0 = 4 * tid; j0 < M; j0 += 1024) {
+      const float4 t = *reinterpret_cast<const float4*>(Tr + j0);
+      const float tv[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int j = j0 + u, c = j >= Bg;
+        const double x = valid[j - c * Bg] ? (double)tv[u] : 0.0;
+        acc[0] += c ? 0.0 : x;
+        acc[1] += c ? x : 0.0;
+      }
+    }
+  } else {
+    for (int j = tid; j < M; j += 256) {
+      const int c = j >= Bg;
+      const double x = valid[j - c * Bg] ? (double)Tr[j] : 0.0;
+      acc[0] += c ? 0.0 : x;
+      acc[1] += c ? x : 0.0;
+    }
+  }
+  const double s0 = minsr_block_sum(acc[0], red);
+  const double s1 = minsr_block_sum(acc[1], red);
+  if (tid == 0) {
+    s[2 * (size_t)row] = s0;
+    s[2 * (size_t)row + 1] = s1;
+  }
+}
+
+// n and g[a][c] = sum_i v_i s[(a, i)][c] / n^2, then s /= n in place (one workgroup).  g[0][1] and
+// g[1][0] are the same number summed in two orders: g[1][0] is stored as g[0][1], so that A is
+// exactly symmetric.
+__global__ __launch_bounds__(256) void minsr_gsum_kernel(const unsigned char* __restrict__ valid, int Bg,
+                                                         double* __restrict__ s, double* __restrict__ g) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  double cnt = 0.0, acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < Bg; i += 256) {
+    if (!valid[i]) continue;
+    cnt += 1.0;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) acc[2 * a + c] += s[2 * ((size_t)a * Bg + i) + c];
+  }
+  double n = minsr_block_sum(cnt, red);
+  double tot[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) tot[k] = minsr_block_sum(acc[k], red);
+  n = n < 1.0 ? 1.0 : n;
+  for (size_t k = tid; k < 4 * (size_t)Bg; k += 256) s[k] /= n;  // every read of s above is behind a barrier
+  if (tid == 0) {
+    g[0] = tot[0] / n / n;
+    g[1] = g[2] = tot[1] / n / n;
+    g[3] = tot[3] / n / n;
+    g[4] = n;
+  }
+}
+
+// pass 2: A[(a,i)][(c,j)] = v_i v_j (T - (r[(a,i)][c] + r[(c,j)][a]) + g[a][c]) / n + damping [row == col];
+// one workgroup per row, two columns per thread and step: a wave reads 512 and writes 1024
+// contiguous bytes per instruction (float4 in and two double2 out per thread left every store
+// instruction with 16-byte holes: 1.40 ms against 1.22 ms at M = 16384).  A is not read again
+// before the solve, so its stores are nontemporal and leave T in the Infinity Cache for the rows
+// that follow (M = 8192: 0.29 -> 0.17 ms)
+template <bool VEC>
+__global__ __launch_bounds__(256) void minsr_matrix_kernel(const float* __restrict__ T,
+                                                           const unsigned char* __restrict__ valid, int Bg,
+                                                           double damping, const double* __restrict__ r,
+                                                           const double* __restrict__ g, double* __restrict__ A) {
+  const int M = 2 * Bg, row = blockIdx.x, tid = threadIdx.x;
+  const int a = row >= Bg;
+  const bool vi = valid[row - a * Bg] != 0;
+  const double n = g[4];
+  const double ri[2] = {r[2 * (size_t)row], r[2 * (size_t)row + 1]};
+  const double ga[2] = {g[2 * a], g[2 * a + 1]};
+  const float* Tr = T + (size_t)row * M;
+  double* Ar = A + (size_t)row * M;
+  auto entry = [&](int j, float t, bool vj, double rj) {
+    const int c = j >= Bg;
+    const double x = vi && vj ? (((double)t - (ri[c] + rj)) + ga[c]) / n : 0.0;
+    return j == row ? x + damping : x;
+  };
+  if (VEC) {
+    typedef double d2_t __attribute__((ext_vector_type(2)));
+    for (int j0 = 2 * tid; j0 < M; j0 += 512) {
+      const float2 t = *reinterpret_cast<const float2*>(Tr + j0);
+      bool vj[2];
+      double rj[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int j = j0 + u;
+        vj[u] = valid[j >= Bg ? j - Bg : j] != 0;
+        rj[u] = r[2 * (size_t)j + a];
+      }
+      d2_t o;
+      o.x = entry(j0, t.x, vj[0], rj[0]);
+      o.y = entry(j0 + 1, t.y, vj[1], rj[1]);
+      __builtin_nontemporal_store(o, reinterpret_cast<d2_t*>(Ar + j0));
+    }
+  } else {
+    for (int j = tid; j < M; j += 256) Ar[j] = entry(j, Tr[j], valid[j >= Bg ? j - Bg : j] != 0, r[2 * (size_t)j + a]);
+  }
+}
+
 }  // namespace
 
 int ntk_tile_walkers(int N) { return N >= 1 && N <= kNtkTileRows ? kNtkTileRows / N : 0; }
 
 void launch_ntk_gram(const float* X, int ldx, int Kx, const float* Y, int ldy, int Ky, const float* arow, int n,
-                     int nwalk, float* T, hipStream_t s) {
+                     int nwalk, int tw_own, int part, int nparts, float* T, hipStream_t s) {
   const int tw = ntk_tile_walkers(n);
   if (tw < 1 || nwalk < 1) return;
   const int nt = (nwalk + tw - 1) / tw;
@@ -228,10 +376,10 @@ void launch_ntk_gram(const float* X, int ldx, int Kx, const float* Y, int ldy, i
   };
   if (vec_ok(X, ldx, Kx) && vec_ok(Y, ldy, Ky))
     hipLaunchKernelGGL(ntk_gram_kernel<true>, dim3(nt, nt), dim3(256), 0, s, X, ldx, Kx, Y, ldy, Ky, arow, n, tw,
-                       nwalk, T);
+                       nwalk, tw_own, part, nparts, T);
   else
     hipLaunchKernelGGL(ntk_gram_kernel<false>, dim3(nt, nt), dim3(256), 0, s, X, ldx, Kx, Y, ldy, Ky, arow, n, tw,
-                       nwalk, T);
+                       nwalk, tw_own, part, nparts, T);
 }
 
 void launch_ntk_centre(const float* X, int ldx, int K, const float* mean, bool bias, int rows, float* U, float* a,
@@ -243,6 +391,25 @@ void launch_ntk_centre(const float* X, int ldx, int K, const float* mean, bool b
 void launch_ntk_mirror(float* T, int B, hipStream_t s) {
   const size_t n = (size_t)B * B;
   hipLaunchKernelGGL(ntk_mirror_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, T, B);
+}
+
+size_t minsr_matrix_ws_doubles(int Bg) { return 4 * (size_t)Bg + 8; }
+
+void launch_minsr_matrix(const float* T, const unsigned char* valid, int Bg, double damping, double* A, double* ws,
+                         hipStream_t s) {
+  const int M = 2 * Bg;
+  double* rs = ws;
+  double* g = ws + 2 * (size_t)M;
+  const bool vec = Bg % 2 == 0 && reinterpret_cast<uintptr_t>(T) % 16 == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0;
+  if (vec)
+    hipLaunchKernelGGL(minsr_rowsum_kernel<true>, dim3(M), dim3(256), 0, s, T, valid, Bg, rs);
+  else
+    hipLaunchKernelGGL(minsr_rowsum_kernel<false>, dim3(M), dim3(256), 0, s, T, valid, Bg, rs);
+  hipLaunchKernelGGL(minsr_gsum_kernel, dim3(1), dim3(256), 0, s, valid, Bg, rs, g);
+  if (vec)
+    hipLaunchKernelGGL(minsr_matrix_kernel<true>, dim3(M), dim3(256), 0, s, T, valid, Bg, damping, rs, g, A);
+  else
+    hipLaunchKernelGGL(minsr_matrix_kernel<false>, dim3(M), dim3(256), 0, s, T, valid, Bg, damping, rs, g, A);
 }
 
 void launch_ntk_mask_ct(const float* logpsi, const float* ct, float* out, int B, hipStream_t s) {

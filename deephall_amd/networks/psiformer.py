@@ -439,12 +439,31 @@ class Psiformer:
         h = get_handle(self.spec, device)
         return int(h.lib.dh_ntk_tile_walkers(h.h))
 
-    def ntk(self, params, data: torch.Tensor, ct: torch.Tensor, logpsi: torch.Tensor | None = None) -> torch.Tensor:
+    def ntk_owner(self, device, walker: int, nparts: int) -> int:
+        """dh_ntk_owner: the part that owns row ``walker`` of the Gram matrix (host only)."""
+        h = get_handle(self.spec, device)
+        return int(h.lib.dh_ntk_owner(h.h, int(walker), int(nparts)))
+
+    def ntk_mirror(self, T: torch.Tensor) -> torch.Tensor:
+        """dh_ntk_mirror in place: the upper triangle of float32 [B, B] onto the lower."""
+        if not (T.is_cuda and T.dtype == torch.float32 and T.dim() == 2 and T.shape[0] == T.shape[1]
+                and T.is_contiguous()):
+            raise ValueError("T must be a contiguous square float32 device matrix")
+        _lib.check(_lib.load().dh_ntk_mirror(_ptr(T), T.shape[0], _stream(T.device)))
+        return T
+
+    def ntk(self, params, data: torch.Tensor, ct: torch.Tensor, logpsi: torch.Tensor | None = None, part: int = 0,
+            nparts: int = 1, mirror: bool = True) -> torch.Tensor:
         """The Gram matrix of the per-walker gradients (dh_ntk): float32 [B, B] with
         T[b, b'] = <g_b, g_b'>, g_b = ct[b,0] dRe log psi_b/dp + ct[b,1] dIm log psi_b/dp over
         the reference parameter tree.  Exactly symmetric and reproducible bit for bit; a walker
         with non-finite log psi or zero ``ct`` has a zero row and column.  The whole batch is
-        one chunk (no silent chunking: the library raises if the workspace cannot hold it)."""
+        one chunk (no silent chunking: the library raises if the workspace cannot hold it).
+
+        ``part`` of ``nparts`` (dh_ntk_part): only the upper-triangle entries whose row
+        ``ntk_owner`` gives to ``part`` are computed, the rest is 0; the parts' sum (an all-reduce
+        across ranks) mirrored is the whole T bit for bit.  ``mirror=False`` leaves the lower
+        triangle 0 (``ntk_mirror`` once, after the sum)."""
         h = self.prepare(params, data.device)
         x = self._check_walkers(data)
         B = x.shape[0]
@@ -454,9 +473,13 @@ class Psiformer:
         T = torch.empty(B, B, dtype=torch.float32, device=x.device)
         need = h.lib.dh_ntk_workspace_bytes(h.h, B)
         ws = h.workspace(max(need, 1))
-        _lib.check(h.lib.dh_ntk(h.h, _ptr(x), B, _ptr(ct), _ptr(T), _ptr(logpsi), _ptr(ws), ws.numel(),
-                                _stream(x.device)))
-        return T
+        if (part, nparts, mirror) == (0, 1, True):
+            _lib.check(h.lib.dh_ntk(h.h, _ptr(x), B, _ptr(ct), _ptr(T), _ptr(logpsi), _ptr(ws), ws.numel(),
+                                    _stream(x.device)))
+            return T
+        _lib.check(h.lib.dh_ntk_part(h.h, _ptr(x), B, _ptr(ct), _ptr(T), _ptr(logpsi), _ptr(ws), ws.numel(), int(part),
+                                     int(nparts), _stream(x.device)))
+        return self.ntk_mirror(T) if mirror else T
 
     # ---- KFAC (optimizers/kfac.py:195-241; dh_kfac_*)
     def kfac_layout(self, device) -> dict:

@@ -13,7 +13,9 @@ all-reduce, the EMA / damped inverses / preconditioned, norm-constrained update 
 device with no host sync (the algorithm is restated in oracle/kfac.py).
 MinSR (not in the reference) takes the exact natural-gradient step in sample
 space: the per-walker gradient Gram matrix comes from the dh_ntk kernels, the 2B x 2B solve
-is float64 torch.linalg on the device, the update direction one more dh_logpsi_vjp.
+is float64 torch.linalg on the device, the update direction one more dh_logpsi_vjp.  Across
+ranks (``optim.minsr.sharded``) every rank computes its share of the Gram matrix of the gathered
+walkers (dh_ntk_part) and the solve matrix comes from one kernel (dh_minsr_matrix).
 """
 
 from __future__ import annotations
@@ -21,6 +23,7 @@ from __future__ import annotations
 import logging
 
 import torch
+import torch.distributed as dist
 
 from . import _lib, constants
 from .config import Config, LearningRate, OptimizerName
@@ -196,14 +199,106 @@ def minsr_direction(net, params: ParamTree, data: torch.Tensor, diff: torch.Tens
     return net.vjp(params, data, ct2)
 
 
+def minsr_matrix(T: torch.Tensor, valid: torch.Tensor, damping: float) -> torch.Tensor:
+    """dh_minsr_matrix: A = C T C / n + damping I, float64 [2B, 2B], from the symmetric float32
+    Gram matrix ``T`` [2B, 2B] of the doubled batch and the walkers' ``valid`` flags [B] (bool);
+    C centres each half over the valid walkers (n of them, at least 1) and zeroes the others.
+    What ``minsr_direction`` assembles in torch, in one kernel: T read twice, A written once."""
+    M = T.shape[0]
+    B = M // 2
+    if not (T.is_cuda and T.dtype == torch.float32 and tuple(T.shape) == (2 * B, 2 * B) and B >= 1):
+        raise ValueError("T must be a float32 [2B, 2B] device matrix")
+    if tuple(valid.shape) != (B,):
+        raise ValueError(f"valid must be [{B}]")
+    T = T.contiguous()
+    v = valid.to(device=T.device, dtype=torch.bool).contiguous().view(torch.uint8)
+    lib = _lib.load()
+    A = torch.empty(M, M, dtype=torch.float64, device=T.device)
+    ws = torch.empty(lib.dh_minsr_matrix_workspace_bytes(B) // 8, dtype=torch.float64, device=T.device)
+    _lib.check(lib.dh_minsr_matrix(_ptr(T), _ptr(v), B, float(damping), _ptr(A), _ptr(ws), ws.numel() * 8,
+                                   _stream(T.device)))
+    return A
+
+
+def minsr_direction_sharded(net, params: ParamTree, data: torch.Tensor, diff: torch.Tensor, damping: float,
+                            keep: dict | None = None) -> ParamTree:
+    """``minsr_direction`` over the walkers of every rank: ``data`` [B, N, 2] and
+    ``diff`` [B, 2] are this rank's shard, the direction is that of the gathered batch of
+    B_g = world size x B walkers, identical on every rank.
+
+    No activations travel: the walkers and diffs are all-gathered (one small collective), every
+    rank runs the forward / reverse pass over all 2 B_g walkers of the doubled batch and the Gram
+    products of the rows it owns (dh_ntk_part), one all-reduce SUM puts T together — exact, every
+    entry has one owner — and dh_ntk_mirror, dh_minsr_matrix and the float64 solve run redundantly
+    on every rank.  The centred solution's slice for this rank's walkers goes through
+    dh_logpsi_vjp; the all-reduce SUM of the results is the direction.  World size 1: the same
+    kernels, no collectives.  Shards must be equal (``ValueError``).
+    ``keep``: a dict that receives T, A and the solution y (tests)."""
+    R, rank = constants.world_size(), constants.rank()
+    B = data.shape[0]
+    dev = data.device
+    diff = diff.to(device=dev, dtype=torch.float32)
+    if R > 1:
+        sizes = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(R)]
+        dist.all_gather(sizes, torch.tensor([B], dtype=torch.int64, device=dev))
+        sizes = [int(s) for s in sizes]
+        if sizes != [B] * R:
+            raise ValueError(f"sharded MinSR needs equal walker shards on every rank, got {sizes}")
+        mine = torch.cat([data.reshape(B, -1).float(), diff], dim=1).contiguous()
+        parts = [torch.empty_like(mine) for _ in range(R)]
+        dist.all_gather(parts, mine)
+        allx = torch.cat(parts)
+        data_g = allx[:, :-2].reshape(R * B, *data.shape[1:]).contiguous()
+        diff_g = allx[:, -2:]
+    else:
+        data_g, diff_g = data, diff
+    Bg = R * B
+    ct = torch.zeros(2 * Bg, 2, dtype=torch.float32, device=dev)
+    ct[:Bg, 0] = 1.0
+    ct[Bg:, 1] = 1.0
+    lp = torch.empty(2 * Bg, 2, dtype=torch.float32, device=dev)
+    T = net.ntk(params, torch.cat([data_g, data_g]), ct, logpsi=lp, part=rank, nparts=R, mirror=False)
+    if R > 1:
+        dist.all_reduce(T)
+    net.ntk_mirror(T)
+    diff_g = diff_g.double()
+    valid = ~torch.isnan(diff_g).any(dim=1) & torch.isfinite(lp[:Bg]).all(dim=1)
+    A = minsr_matrix(T, valid, damping)
+    if keep is not None:
+        keep["T"], keep["A"] = T, A.clone()
+    del T
+    v = valid.double()
+    n = v.sum().clamp(min=1.0)
+    eps = (torch.nan_to_num(diff_g, nan=0.0) * v[:, None]).t().reshape(2 * Bg) / n.sqrt()
+    L, info = torch.linalg.cholesky_ex(A)
+    if int(info) == 0:
+        y = torch.cholesky_solve(eps[:, None], L)[:, 0]
+    else:
+        y = torch.linalg.solve(A, eps)
+    del L, A
+    if keep is not None:
+        keep["y"] = y
+    y2 = y.view(2, Bg) * v
+    y2 = y2 - v * (y2.sum(-1, keepdim=True) / n)
+    ct2 = (2.0 * y2 / n.sqrt()).t()[rank * B:(rank + 1) * B].contiguous().float()
+    delta = net.vjp(params, data, ct2)
+    if R > 1:
+        dist.all_reduce(delta.flat)  # a sum: every row carries the global 1 / sqrt(n)
+    return delta
+
+
 def make_minsr_training_step(cfg: Config, network):
     """MinSR (Chen & Heyl 2024; Rende et al. 2024): stochastic reconfiguration solved in sample
     space, delta = (S + damping I)^-1 g with S the centred 2B-sample Fisher matrix — exact, where
     KFAC approximates — then KFAC's norm constraint against the ENERGY_GRAD gradient g:
-    c = min(1, sqrt(norm_constraint / (lr^2 <delta, g>))), params -= lr c delta."""
-    if constants.world_size() > 1:
-        raise NotImplementedError("MinSR on more than one rank needs an all-gather of the walkers' Gram rows "
-                                  "(pairs of walkers on different ranks); run it on a single rank")
+    c = min(1, sqrt(norm_constraint / (lr^2 <delta, g>))), params -= lr c delta.
+    ``optim.minsr.sharded``: the direction over the walkers of every rank
+    (minsr_direction_sharded) and g averaged over ranks as the Adam step's."""
+    sharded = bool(cfg.optim.minsr.sharded)
+    if constants.world_size() > 1 and not sharded:
+        raise NotImplementedError("MinSR on more than one rank needs each rank to compute a share of the gathered "
+                                  "walkers' Gram matrix: set optim.minsr.sharded (every rank then holds the whole "
+                                  "batch's activations and matrices), or run it on a single rank")
     loss_fn = make_loss_fn(network, cfg.system, LossMode.ENERGY_DIFF)
     net = loss_fn.network
     if net is None or not hasattr(net, "ntk"):
@@ -220,7 +315,11 @@ def make_minsr_training_step(cfg: Config, network):
         diff = torch.view_as_real(diff).contiguous()
         nvalid = (~torch.isnan(diff).any(dim=1)).sum().float().view(1)
         grad = net.vjp(params, data, grad_cotangent(diff, nvalid, 0))
-        delta = minsr_direction(net, params, data, diff, opt.damping)
+        if sharded:
+            constants.pmean_(grad.flat)
+            delta = minsr_direction_sharded(net, params, data, diff, opt.damping)
+        else:
+            delta = minsr_direction(net, params, data, diff, opt.damping)
         lr = lr_schedule(opt.lr, opt_state.step)
         d = torch.nan_to_num(delta.flat, nan=0.0, posinf=0.0, neginf=0.0)
         sq = (lr * lr) * torch.dot(d.double(), torch.nan_to_num(grad.flat).double())

@@ -190,11 +190,43 @@ int dh_kfac_step(dh_handle* h, float* raw, const float* stats, float ema, float 
  *   before any device call); "sparse" orbitals and Laughlin handles are DH_EINVAL.
  * dh_ntk_tile_walkers: walkers per Gram tile (host only; tile_walkers * N <= 128 rows, a
  *   workgroup owns one pair of tiles); 0 for a handle dh_ntk does not serve.
- * The launches are not recorded by dh_profile_* (no kernel class is theirs). */
+ * The launches are not recorded by dh_profile_* (no kernel class is theirs).
+ *
+ * Across ranks every rank holds all B walkers and computes a share of T:
+ * dh_ntk_part: dh_ntk's arguments and checks, then DH_EINVAL unless 0 <= part < nparts (all
+ *   before any device call).  T is cleared and only the entries T[b][b'], b <= b', with
+ *   dh_ntk_owner(h, b, nparts) == part are accumulated; no mirror.  The forward pass, the
+ *   centring and logpsi cover all B walkers, identically for every part.  The parts have
+ *   disjoint support, so their sum in any order (an all-reduce) followed by dh_ntk_mirror is
+ *   dh_ntk's T bit for bit; dh_ntk is part 0 of 1 and the mirror.  Workspace as dh_ntk.
+ * dh_ntk_mirror: T[b'][b] = T[b][b'] for b < b', T float32 [B][B] on the device.
+ * dh_ntk_owner: (walker / dh_ntk_tile_walkers(h)) % nparts (host only): the part that owns row
+ *   `walker` of T — a property of the row, not of a launch's tile size, so that all additions to
+ *   an entry happen on one rank in one order.  -1 for a handle dh_ntk rejects, walker < 0 or
+ *   nparts < 1.  Rows are dealt out cyclically by tile: the first and the last part's share of
+ *   the upper triangle differ by about 2 (nparts - 1) / (number of tiles), relative.
+ *
+ * dh_minsr_matrix: the matrix MinSR solves, from T float32 [M][M] symmetric, M = 2 Bg, rows
+ *   (a, i) = a Bg + i over the halves a (Re | Im) and walkers i, and valid [Bg] (bytes, nonzero =
+ *   the walker takes part; n = max(1, their number)):
+ *     r[a,i][c] = sum_j v_j T[(a,i),(c,j)] / n,   g[a][c] = sum_i v_i r[a,i][c] / n,
+ *     A[(a,i),(c,j)] = v_i v_j (T - r[a,i][c] - r[c,j][a] + g[a][c]) / n + damping [(a,i) == (c,j)]
+ *   A float64 [M][M], WRITTEN once; T is read twice (row sums in double in a fixed order, then
+ *   the assembly); no atomics: two calls give identical bits; A is exactly symmetric; an invalid
+ *   walker's rows and columns are 0 with damping on the diagonal.  ws: 8-byte aligned device
+ *   memory of dh_minsr_matrix_workspace_bytes(Bg); a null pointer is DH_EINVAL, a short workspace
+ *   DH_ENOMEM, both before any device call. */
 size_t dh_ntk_workspace_bytes(const dh_handle* h, int batch);
 int dh_ntk_tile_walkers(const dh_handle* h);
 int dh_ntk(dh_handle* h, const float* x, int B, const float* ct, float* T, float* logpsi, void* ws, size_t ws_bytes,
            void* stream);
+int dh_ntk_part(dh_handle* h, const float* x, int B, const float* ct, float* T, float* logpsi, void* ws,
+                size_t ws_bytes, int part, int nparts, void* stream);
+int dh_ntk_mirror(float* T, int B, void* stream);
+int dh_ntk_owner(const dh_handle* h, int walker, int nparts);
+size_t dh_minsr_matrix_workspace_bytes(int Bg);
+int dh_minsr_matrix(const float* T, const unsigned char* valid, int Bg, double damping, double* A, void* ws,
+                    size_t ws_bytes, void* stream);
 
 /* Cotangents of the gradient estimator 2 nanmean(conj(d log psi) diff) (loss.py:59-64):
  * part 0 (its real part, ENERGY_GRAD): ct = 2 (Re diff, Im diff) / n;

@@ -9,7 +9,13 @@ Gram products' algorithmic rate
     FLOP = 2 * (R^2 / 2) * sum over dense maps (K_in + K_out),  R = walkers * N rows
 
 over the whole call's time and over the call's time less the VJP's, against the 157.3 TF/s f32
-matrix peak.  usage: ntk_bench.py [B] [NSPINS FLUX] [reps]"""
+matrix peak.
+
+``--parts R`` (repeatable) also times what sharded MinSR adds: dh_ntk_part(0 of 1) + dh_ntk_mirror
+(the same work as dh_ntk), dh_ntk_part(p of R) for every p on this one GPU — the slowest against
+1 / R of the whole — and dh_minsr_matrix against the float64 torch assembly of
+optimizers.minsr_direction and against its traffic of 16 M^2 bytes (T read twice, A written once).
+usage: ntk_bench.py [B] [NSPINS FLUX] [reps] [--parts R]..."""
 import statistics
 import sys
 from pathlib import Path
@@ -24,6 +30,11 @@ from deephall_amd.train import init_guess  # noqa: E402
 
 PEAK_F32_MATRIX = 157.3e12
 
+parts_list = []
+while "--parts" in sys.argv:
+    i = sys.argv.index("--parts")
+    parts_list.append(int(sys.argv[i + 1]))
+    del sys.argv[i:i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 nspins = (int(sys.argv[2]), 0) if len(sys.argv) > 2 else (6, 0)
 flux = int(sys.argv[3]) if len(sys.argv) > 3 else 15
@@ -74,3 +85,53 @@ print(f"Gram FLOP / whole call: {whole / 1e12:6.1f} TF/s = {whole / PEAK_F32_MAT
 if ntk[0] > vjp[0]:
     net = flop / ((ntk[0] - vjp[0]) * 1e-3)
     print(f"Gram FLOP / (call - VJP): {net / 1e12:6.1f} TF/s = {net / PEAK_F32_MATRIX:.3f} of peak")
+
+if parts_list:
+    from deephall_amd.optimizers import minsr_matrix  # noqa: E402
+
+    one = timed(lambda: model.ntk(params, x2, ct, part=0, nparts=1, mirror=True))
+    print(f"dh_ntk_part(0 of 1) + dh_ntk_mirror {one[0]:9.2f} ms  (min {one[1]:.2f}, max {one[2]:.2f}): "
+          f"{one[0] / ntk[0]:.4f} of dh_ntk")
+    for R_ in parts_list:
+        ts = [timed(lambda p=p: model.ntk(params, x2, ct, part=p, nparts=R_, mirror=False)) for p in range(R_)]
+        med = [t[0] for t in ts]
+        print(f"dh_ntk_part(p of {R_}): " + " ".join(f"{m:.2f}" for m in med) + " ms")
+        print(f"  slowest {max(med):.2f} ms = {max(med) / (ntk[0] / R_):.3f} of dh_ntk / {R_} ({ntk[0] / R_:.2f} ms); "
+              f"fastest {min(med):.2f} ms; less the VJP's {vjp[0]:.2f} ms every part repeats: "
+              f"{(max(med) - vjp[0]) / ((ntk[0] - vjp[0]) / R_):.3f} of the Gram products' share")
+
+    def matrix_bench(T, label):
+        M = T.shape[0]
+        Bg = M // 2
+        valid = torch.ones(Bg, dtype=torch.bool, device="cuda")
+        valid[Bg // 3] = False
+
+        def torch_assembly():
+            Td = T.double()
+            v = valid.double()
+            n = v.sum().clamp(min=1.0)
+
+            def centre(a):
+                a = a * v
+                return a - v * (a.sum(-1, keepdim=True) / n)
+
+            T4 = centre(Td.view(2, Bg, 2, Bg))
+            T4 = centre(T4.permute(2, 3, 0, 1)).permute(2, 3, 0, 1)
+            return T4.reshape(M, M) / n + 1e-3 * torch.eye(M, dtype=torch.float64, device="cuda")
+
+        ref = torch_assembly()
+        err = float((minsr_matrix(T, valid, 1e-3) - ref).abs().max() / ref.abs().max())
+        del ref
+        fused = timed(lambda: minsr_matrix(T, valid, 1e-3))
+        eager = timed(torch_assembly)
+        byts = 16.0 * M * M
+        print(f"dh_minsr_matrix ({label}, M = {M}) {fused[0]:9.3f} ms  (min {fused[1]:.3f}, max {fused[2]:.3f}): "
+              f"{byts / (fused[0] * 1e-3) / 1e12:.2f} TB/s of 16 M^2 = {byts / 1e9:.2f} GB; "
+              f"torch assembly {eager[0]:.2f} ms (min {eager[1]:.2f}, max {eager[2]:.2f}), {eager[0] / fused[0]:.1f} x; "
+              f"max |difference| / max |A| {err:.2e}")
+
+    matrix_bench(model.ntk(params, x2, ct), "this call's T")
+    # twice the walkers (two ranks' gathered batch): a synthetic symmetric T, past the 256 MiB Infinity Cache
+    S = torch.randn(4 * B, 4 * B, device="cuda")
+    S = S + S.t()
+    matrix_bench(S, "synthetic T of twice the walkers")
