@@ -88,6 +88,8 @@ EXPORTS = [
     "dh_ntk_owner",
     "dh_minsr_matrix_workspace_bytes",
     "dh_minsr_matrix",
+    "dh_ntk_jvp_workspace_bytes",
+    "dh_ntk_jvp",
 ]
 
 
@@ -229,6 +231,10 @@ def load(path: Path | str | None = None):
     lib.dh_minsr_matrix_workspace_bytes.restype = sz
     lib.dh_minsr_matrix.argtypes = [vp, vp, i32, C.c_double, vp, vp, sz, vp]
     lib.dh_minsr_matrix.restype = i32
+    lib.dh_ntk_jvp_workspace_bytes.argtypes = [vp, i32]
+    lib.dh_ntk_jvp_workspace_bytes.restype = sz
+    lib.dh_ntk_jvp.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]
+    lib.dh_ntk_jvp.restype = i32
     lib.dh_grad_cotangent.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.dh_grad_cotangent.restype = i32
     lib.dh_adam_update.argtypes = [vp, vp, vp, vp, sz, f32, f32, f32, f32, i32, vp]

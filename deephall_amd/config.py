@@ -120,12 +120,14 @@ class OptimizerMinsr:
     its values.  ``sharded``: the Gram matrix is computed in shares across the ranks
     (optimizers.minsr_direction_sharded); opt-in, because every rank then holds the gathered
     batch's activations and the (2 x global batch)^2 matrices.  Without it MinSR runs on one rank
-    only."""
+    only.  ``momentum``: SPRING's mu (Goldshlager, Abrahamsen, Lin 2024), 0 <= mu < 1; the
+    damping then pulls the step towards mu x the previous one instead of towards 0.  0: MinSR."""
 
     lr: LearningRate = field(default_factory=lambda: LearningRate(rate=0.05))
     damping: float = 1e-3
     norm_constraint: float = 1e-3
     sharded: bool = False
+    momentum: float = 0.0
 
 
 @dataclass

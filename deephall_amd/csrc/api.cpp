@@ -1320,14 +1320,17 @@ int run_vjp(dh_handle* h, const float* x, int nw, const float* ct, float* grad, 
 
 // Workspace of dh_ntk over nw walkers: the VJP's (one chunk), then the masked cotangents, one
 // LayerNorm's per-walker scale | bias tangents [nw][2 D], and one dense map's centred input
-// rows [rows][D], their offsets [rows] and mean row [D]
+// rows [rows][D], their offsets [rows] and mean row [D].  dh_ntk_jvp (jvp) adds one dense map's
+// slice of the direction, packed [K_in + 1 bias row][K_out] and sized to the largest map, its
+// per-column constant and the column blocks' partial sums [blocks][nw].
 struct NtkWork {
   GradWork g;
   float *ctm, *lnp, *xc, *arow, *mean;
+  float *vpk, *cvec, *jpart;  // dh_ntk_jvp only
   size_t total_bytes;
 };
 
-NtkWork carve_ntk(const Dims& d, int nw, void* base) {
+NtkWork carve_ntk(const Dims& d, int nw, void* base, bool jvp = false) {
   NtkWork w{};
   w.g = carve_grad(d, nw, base);
   size_t off = w.g.total_bytes / sizeof(float);
@@ -1341,6 +1344,12 @@ NtkWork carve_ntk(const Dims& d, int nw, void* base) {
   w.xc = take((size_t)nw * d.N * std::max(d.D, 4));
   w.arow = take((size_t)nw * d.N);
   w.mean = take((size_t)std::max(d.D, 4));
+  if (jvp) {
+    const size_t kout = std::max((size_t)3 * d.D, (size_t)d.ld_orb);
+    w.vpk = take(((size_t)d.D + 1) * kout);
+    w.cvec = take(kout);
+    w.jpart = take((size_t)ntk_jvp_col_blocks((int)kout) * nw);
+  }
   w.total_bytes = off * sizeof(float);
   return w;
 }
@@ -1352,8 +1361,13 @@ NtkWork carve_ntk(const Dims& d, int nw, void* base) {
 // J J^T of their explicit per-walker tangents.  T must be zero at entry; the upper triangle of
 // tile pairs is accumulated, of the rows that part `part` of `nparts` owns (ntk.hip "Sharding");
 // the caller mirrors it.
+// With a direction v (flat, dh_ref_layout) the same walk adds <g_b, v> into jv [nw] (zero at
+// entry), for every walker whatever the part: next to each map's Gram launch, launch_ntk_jvp on
+// the same centred rows and tangents against the map's slice of v (as it lies, or packed into
+// nt.vpk where the map's columns come from several leaves); launch_ntk_rowdot for the explicit
+// rows.  T == null (with v): no Gram launches.
 int ntk_backward(dh_handle* h, const float* x, int nw, const float* ct, float* T, const NtkWork& nt, int part,
-                 int nparts, hipStream_t s) {
+                 int nparts, hipStream_t s, const float* v = nullptr, float* jv = nullptr) {
   const Dims& d = h->d;
   const Params& P = h->p;
   const GradWork& w = nt.g;
@@ -1371,48 +1385,77 @@ int ntk_backward(dh_handle* h, const float* x, int nw, const float* ct, float* T
   // one dense map: input rows X [rows][kx] (augmented with a 1 when the map has a bias),
   // output tangents dY [rows][ky]
   // (kx <= D; the rows are centred on their batch mean first, ntk.hip "Precision")
-  auto gram = [&](const float* X, int ldx, int kx, const float* dY, int ldy, int ky, bool bias) {
+  // (V [kx][ky] with row stride ldv, vb [ky] or null: the direction's slices for the map)
+  auto gram = [&](const float* X, int ldx, int kx, const float* dY, int ldy, int ky, bool bias, const float* V,
+                  int ldv, const float* vb) {
     launch_colsum_partial(X, ldx, rows, kx, w.P, s);
     launch_reduce2d(w.P, grad_chunks(rows), (size_t)kx, kx, 1, kx, nt.mean, kx, 1.f / (float)rows, 0, s);
     launch_ntk_centre(X, ldx, kx, nt.mean, bias, rows, nt.xc, nt.arow, s);
-    launch_ntk_gram(nt.xc, kx, kx, dY, ldy, ky, nt.arow, N, nw, tw_own, part, nparts, T, s);
+    if (T) launch_ntk_gram(nt.xc, kx, kx, dY, ldy, ky, nt.arow, N, nw, tw_own, part, nparts, T, s);
+    if (v) {
+#ifdef DH_NTK_JVP_RAW  // A/B builds only (tools/build_variant.sh): the raw rows, DESIGN.md §3g
+      launch_ntk_jvp_cvec(nullptr, kx, V, ldv, vb, ky, nt.cvec, s);
+      launch_ntk_jvp(X, ldx, kx, V, ldv, nt.cvec, dY, ldy, ky, N, nw, nt.jpart, jv, s);
+#else
+      // (x V + v_b) . dy = (u V + (m V + v_b)) . dy
+      launch_ntk_jvp_cvec(nt.mean, kx, V, ldv, vb, ky, nt.cvec, s);
+      launch_ntk_jvp(nt.xc, kx, kx, V, ldv, nt.cvec, dY, ldy, ky, N, nw, nt.jpart, jv, s);
+#endif
+    }
   };
-  // explicit per-walker tangents J [nw][k]: T += J J^T
-  auto gram_rows = [&](const float* J, int k) {
-    launch_ntk_gram(J, k, k, nullptr, 0, 0, nullptr, 1, nw, tw_own, part, nparts, T, s);
+  // explicit per-walker tangents J [nw][ka + kb]: T += J J^T; va, vb: their two leaves of v
+  auto gram_rows = [&](const float* J, int ka, int sega, int kb, int segb) {
+    if (T) launch_ntk_gram(J, ka + kb, ka + kb, nullptr, 0, 0, nullptr, 1, nw, tw_own, part, nparts, T, s);
+    if (v) launch_ntk_rowdot(J, ka + kb, v + h->ref_offsets[sega], ka, v + h->ref_offsets[segb], kb, nw, jv, s);
   };
+  auto vs = [&](int seg) { return v ? v + h->ref_offsets[seg] : nullptr; };
   launch_det_bwd(d, w.F, x, P.jastrow, h->norm, ct, w.dF, w.jg, nw, s);
-  gram_rows(w.jg, 2);
+  gram_rows(w.jg, 1, RS.jas(0), 1, RS.jas(1));
   // the orbital DenseGenerals: a row's dF is zero in the other spin block's columns, so the
   // blocks' Gram products add up to the one over all orb_cols
   // (columns rounded up to 4 for the kernel's float4 loads: det_bwd writes the padding 0)
-  gram(w.hs[d.L], D, D, w.dF, d.ld_orb, round_up(d.orb_cols, 4), true);
+  float* vpb = v ? nt.vpk + (size_t)D * std::max(3 * D, d.ld_orb) : nullptr;  // the packed maps' bias row
+  if (v) {  // kernels | biases at columns i MNK of ld_orb, the padding 0 (as pack_from_ref)
+    const int MNK = d.M * d.N * d.K;
+    launch_copy2d(nullptr, 0, nt.vpk, d.ld_orb, D, d.ld_orb, s);
+    launch_copy2d(nullptr, 0, vpb, d.ld_orb, 1, d.ld_orb, s);
+    for (int i = 0; i < 2 * d.NB; ++i) {
+      launch_copy2d(vs(RS.orb_kernel(i)), MNK, nt.vpk + i * MNK, d.ld_orb, D, MNK, s);
+      launch_copy2d(vs(RS.orb_bias(i)), MNK, vpb + i * MNK, d.ld_orb, 1, MNK, s);
+    }
+  }
+  gram(w.hs[d.L], D, D, w.dF, d.ld_orb, round_up(d.orb_cols, 4), true, nt.vpk, d.ld_orb, vpb);
   bwd(w.dF, d.ld_orb, P.WorbB, P.WorbBT, nullptr, w.dh);
   for (int l = d.L - 1; l >= 0; --l) {
     const LayerParams& lp = P.layer[l];
     // LN2: per-walker scale | bias tangents (N rows per block), dU -> dA, dz
     launch_ln_bwd_rows(w.h1[l], w.z[l], lp.ln2, w.dh, nullptr, w.dA, w.dz, nt.lnp, rows, D, N, s);
-    gram_rows(nt.lnp, 2 * D);
-    gram(w.h1[l], D, D, w.dz, D, D, true);      // Wm, bm
+    gram_rows(nt.lnp, D, RS.lay(l, Rln2s), D, RS.lay(l, Rln2b));
+    gram(w.h1[l], D, D, w.dz, D, D, true, vs(RS.lay(l, RWm)), D, vs(RS.lay(l, Rbm)));  // Wm, bm
     bwd(w.dz, D, lp.WmB, lp.WmBT, w.dA, w.dh);  // dh1 = dU + dz Wm^T
     launch_ln_bwd_rows(w.t[l], nullptr, lp.ln1, w.dh, nullptr, w.dA, nullptr, nt.lnp, rows, D, N, s);
-    gram_rows(nt.lnp, 2 * D);
+    gram_rows(nt.lnp, D, RS.lay(l, Rln1s), D, RS.lay(l, Rln1b));
     // t = h + (o Wo + bo) Wl, the kernels' folded map taken apart again (w.dO, w.dWol: scratch)
     //   Wo, bo: input [o, 1], output tangent dT Wl^T
     launch_transpose(ref(RS.lay(l, RWl)), D, D, D, w.dWol, D, s);
     launch_gemm(w.dA, D, w.dWol, D, nullptr, nullptr, 0, w.dO, D, rows, D, D, 1, s);
-    gram(w.o[l], D, D, w.dO, D, D, true);
+    gram(w.o[l], D, D, w.dO, D, D, true, vs(RS.lay(l, RWo)), D, vs(RS.lay(l, Rbo)));
     //   Wl (no bias): input o Wo + bo, output tangent dT
     launch_gemm(w.o[l], D, ref(RS.lay(l, RWo)), D, ref(RS.lay(l, Rbo)), nullptr, 0, w.dO, D, rows, D, D, 1, s);
-    gram(w.dO, D, D, w.dA, D, D, false);
+    gram(w.dO, D, D, w.dA, D, D, false, vs(RS.lay(l, RWl)), D, nullptr);
     bwd(w.dA, D, lp.WolB, lp.WolBT, nullptr, w.dO);  // dO = dT Wol^T
     launch_attn_bwd(d, w.qkv[l], w.dO, w.dqkv, nw, s);
-    gram(w.hs[l], D, D, w.dqkv, 3 * D, 3 * D, true);      // Wq | Wk | Wv and their biases
-    bwd(w.dqkv, 3 * D, lp.WqkvB, lp.WqkvBT, w.dA, w.dh);  // dh_l = dT + dqkv Wqkv^T
+    if (v)  // Wq | Wk | Wv side by side, their biases below (as pack_from_ref)
+      for (int p3 = 0; p3 < 3; ++p3) {
+        launch_copy2d(vs(RS.lay(l, RWq + 2 * p3)), D, nt.vpk + p3 * D, 3 * D, D, D, s);
+        launch_copy2d(vs(RS.lay(l, Rbq + 2 * p3)), D, vpb + p3 * D, 3 * D, 1, D, s);
+      }
+    gram(w.hs[l], D, D, w.dqkv, 3 * D, 3 * D, true, nt.vpk, 3 * D, vpb);  // Wq | Wk | Wv and their biases
+    bwd(w.dqkv, 3 * D, lp.WqkvB, lp.WqkvBT, w.dA, w.dh);                  // dh_l = dT + dqkv Wqkv^T
   }
   // h_0 = features W0 (no bias)
   launch_ntk_features(d, w.geo, rows, w.dO, s);
-  gram(w.dO, 4, 4, w.dh, D, D, false);
+  gram(w.dO, 4, 4, w.dh, D, D, false, vs(RS.W0()), D, nullptr);
   return check_launch();
 }
 
@@ -1663,6 +1706,38 @@ int dh_ntk_part(dh_handle* h, const float* x, int B, const float* ct, float* T, 
                 size_t ws_bytes, int part, int nparts, void* stream) {
   if (int rc = ntk_check(h, x, B, ct, T, ws, ws_bytes, part, nparts)) return rc;
   return ntk_run(h, x, B, ct, T, logpsi, ws, part, nparts, (hipStream_t)stream);
+}
+
+size_t dh_ntk_jvp_workspace_bytes(const dh_handle* h, int batch) {
+  if (!h || h->laughlin || h->d.sparse || batch < 1) return 0;
+  return carve_ntk(h->d, batch, nullptr, /*jvp=*/true).total_bytes;
+}
+
+int dh_ntk_jvp(dh_handle* h, const float* x, int B, const float* ct, const float* v, float* T, float* jv,
+               float* logpsi, void* ws, size_t ws_bytes, int part, int nparts, void* stream) {
+  // dh_ntk_part's checks (T may be null), then this call's own: all before the first device call
+  if (!h) return fail(DH_EINVAL, "null handle");
+  if (h->laughlin) return fail(DH_EINVAL, "the Laughlin wavefunction has no parameters to differentiate");
+  if (h->d.sparse) return fail(DH_EINVAL, "dh_ntk_jvp supports orbital type \"full\" only");
+  if (!x || B < 1) return fail(DH_EINVAL, "bad walkers");
+  if (!ct || !v || !jv) return fail(DH_EINVAL, "null argument");
+  if (h->d.D > 1024 || h->d.dh > 1024) return fail(DH_EINVAL, "dh_ntk_jvp supports D <= 1024");
+  if (h->d.N > 32 || h->d.L > 16) return fail(DH_EINVAL, "dh_ntk_jvp supports N <= 32, L <= 16");
+  if (nparts < 1 || part < 0 || part >= nparts) return fail(DH_EINVAL, "dh_ntk_jvp needs 0 <= part < nparts");
+  if (!T && nparts != 1) return fail(DH_EINVAL, "dh_ntk_jvp without T is part 0 of 1");
+  if (!ws || ws_bytes < dh_ntk_jvp_workspace_bytes(h, B))
+    return fail(DH_ENOMEM, "workspace too small: dh_ntk_jvp takes the whole batch in one chunk");
+  if (!h->params_set) return fail(DH_ESTATE, "parameters not set");
+  if (!h->ref_set) return fail(DH_ESTATE, "dh_ntk_jvp needs parameters uploaded with dh_set_params_ref");
+  hipStream_t s = (hipStream_t)stream;
+  const NtkWork w = carve_ntk(h->d, B, ws, /*jvp=*/true);
+  float* lp = logpsi ? logpsi : w.g.logpsi;
+  if ((T && hipMemsetAsync(T, 0, (size_t)B * B * sizeof(float), s) != hipSuccess) ||
+      hipMemsetAsync(jv, 0, (size_t)B * sizeof(float), s) != hipSuccess)
+    return fail(DH_EHIP, "dh_ntk_jvp: clearing T / jv failed");
+  vjp_forward(h, x, B, lp, w.g, s);
+  launch_ntk_mask_ct(lp, ct, w.ctm, B, s);
+  return ntk_backward(h, x, B, w.ctm, T, w, part, nparts, s, v, jv);
 }
 
 int dh_ntk_mirror(float* T, int B, void* stream) {

@@ -460,6 +460,19 @@ void launch_ntk_gram(const float* X, int ldx, int Kx, const float* Y, int ldy, i
 // X_t . X_t' + bias = U_t . U_t' + a_t + a_t'
 void launch_ntk_centre(const float* X, int ldx, int K, const float* mean, bool bias, int rows, float* U, float* a,
                        hipStream_t s);
+// jv[w] += sum_{t in w, c < Ky} ((X V)[t][c] + cvec[c]) dY[t][c]: X [nwalk n][K], V [K][Ky] (row
+// stride ldv), cvec [Ky] or null, dY [nwalk n][Ky]; one workgroup per tile of ntk_tile_walkers(n)
+// walkers and block of 128 columns, its sums into part [ntk_jvp_col_blocks(Ky)][nwalk] (scratch),
+// then the blocks summed in order into jv
+int ntk_jvp_col_blocks(int Ky);
+void launch_ntk_jvp(const float* X, int ldx, int K, const float* V, int ldv, const float* cvec, const float* dY,
+                    int ldy, int Ky, int n, int nwalk, float* part, float* jv, hipStream_t s);
+// cvec[c] = bias[c] + sum_k mean[k] V[k][c]; bias, mean: null = 0
+void launch_ntk_jvp_cvec(const float* mean, int K, const float* V, int ldv, const float* bias, int Ky, float* cvec,
+                         hipStream_t s);
+// jv[w] += J[w][0 : ka] . va + J[w][ka : ka + kb] . vb
+void launch_ntk_rowdot(const float* J, int ldj, const float* va, int ka, const float* vb, int kb, int nwalk, float* jv,
+                       hipStream_t s);
 void launch_ntk_mirror(float* T, int B, hipStream_t s);
 void launch_ntk_mask_ct(const float* logpsi, const float* ct, float* out, int B, hipStream_t s);
 void launch_ntk_features(const Dims& d, const float* geo, int rows, float* out, hipStream_t s);

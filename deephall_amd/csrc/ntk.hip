@@ -38,6 +38,17 @@
 // workgroup (tile = tw_dense walkers) leaves at once unless its tile row is the part's; a
 // per-walker-row launch (tile = 128 walkers) computes its tile and masks the final add.
 //
+// The Jacobian-vector product (dh_ntk_jvp; SPRING's O phi_prev): jv[b] = <g_b, v> for a parameter
+// direction v, by the same identity on the same rows.  With V, v_b the direction's slices for
+// the map,
+//   <dW_b, V> + <db_b, v_b> = sum_{t in b} (x_t V + v_b) . dy_t
+// — one rows x K_in x K_out product, multiplied element by element with dY and summed over
+// each walker's rows (ntk_jvp_kernel; a workgroup owns one walker tile and one block of 128
+// output columns, and the blocks' sums are added to jv in block order).  It contracts the
+// centred rows u = x - m that the Gram launch of the map has just made; the common part goes
+// into the per-column constant cvec = m V + v_b (ntk_jvp_cvec_kernel).  The explicit per-walker rows are short dot products
+// (ntk_rowdot_kernel).  Linear in v, every sum in a fixed order: jvp(2 v) = 2 jvp(v) bit for bit.
+//
 // minsr_rowsum / minsr_gsum / minsr_matrix kernels (dh_minsr_matrix): the float64 matrix MinSR
 // solves, A = C T C / n + damping I with C the centring over the valid walkers, from the float32
 // T in two passes over it and one write of A.
@@ -181,6 +192,187 @@ __global__ __launch_bounds__(256) void ntk_gram_kernel(const float* __restrict__
       for (int j = 0; j < n; ++j) s += sm[(bi * n + i) * kNtkTileRows + bj * n + j];
     T[(size_t)wi * nwalk + wj] += s;
   }
+}
+
+constexpr int kJvpCols = 128;    // output columns per block of the JVP kernel
+constexpr int kJvpLdV = 136;     // LDS row stride of the staged V panel: rows k and k + 4 lie 32 banks apart
+constexpr int kJvpLdR = 65;      // row stride of the final [128][64] reduction image
+
+// part[blockIdx.y][w] = sum_{t in w} sum_c ((X V)[t][c] + cvec[c]) dY[t][c] over the 128 columns
+// c of block blockIdx.y, for the tw walkers of tile blockIdx.x (header, "The Jacobian-vector
+// product"): X [rows][K], V [K][Ky] (row stride ldv), cvec [Ky] (null: 0), dY [rows][Ky], part
+// [ceil(Ky / 128)][nwalk].  The workgroup streams K through LDS 32 columns at a time (the X tile as
+// the Gram kernel stages it, the V panel [32][128] as it lies), the next step fetched into
+// registers under the current MFMAs, and multiplies the 128 x 128 product by dY in registers,
+// one partial sum per accumulator row and lane.  Rows past the tile / the batch and columns past
+// Ky contribute 0.  The 64 partials of a row (2 waves x 32 lanes) are summed from LDS in a fixed
+// order, then each walker's n rows.  Every column block has its own workgroup whatever the
+// batch — a small batch still fills the machine, and the sum over the blocks
+// (ntk_jvp_reduce_kernel, block order) does not depend on how they were scheduled: no atomics.
+template <bool VEC>
+__global__ __launch_bounds__(256, 2) void ntk_jvp_kernel(const float* __restrict__ X, int ldx, int K,
+                                                         const float* __restrict__ V, int ldv,
+                                                         const float* __restrict__ cvec,
+                                                         const float* __restrict__ dY, int ldy, int Ky, int n,
+                                                         int tw, int nwalk, float* __restrict__ part) {
+  // staging: the X tile [128][kNtkLd] and the V panel [32][kJvpLdV]; at the end the [128][kJvpLdR] image
+  __shared__ float sm[kNtkTileRows * kNtkLd + kNtkKB * kJvpLdV];
+  __shared__ float srow[kNtkTileRows];
+  static_assert(kNtkTileRows * kJvpLdR <= kNtkTileRows * kNtkLd + kNtkKB * kJvpLdV, "reduction image fits");
+  const int I = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int l32 = lane & 31, lh = lane >> 5;
+  const int wr = (w >> 1) * 64, wc = (w & 1) * 64;
+  const int tr = tw * n, rows = nwalk * n;
+  const int nval = min(tr, rows - I * tr);  // rows of this tile that exist
+  float* sA = sm;
+  float* sV = sm + kNtkTileRows * kNtkLd;
+  const int fr = tid >> 3, fc = (tid & 7) * 4;    // X: rows fr + 32 q, columns fc .. fc + 3 of the step
+  const int vr = tid >> 5, vc = (tid & 31) * 4;   // V: rows vr + 8 q of the step, columns vc .. vc + 3 of the block
+  float rs[2][16];  // this lane's partial of row wr + 32 a + (e & 3) + 8 (e >> 2) + 4 lh
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) rs[a][e] = 0.f;
+  const int c0 = blockIdx.y * kJvpCols;
+  {
+    f32x16_n g[2][2];  // [row half][column half]
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) g[a][b][e] = 0.f;
+    float4 fa[4], fv[4];
+    auto fetch = [&](int k0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int r = fr + 32 * q, ra = I * tr + r, kv = k0 + vr + 8 * q;
+        fa[q] = ntk_load4<VEC>(X, ldx, K, ra, k0 + fc, r < tr && ra < rows);
+        fv[q] = ntk_load4<VEC>(V, ldv, Ky, kv, c0 + vc, kv < K);
+      }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < K; k0 += kNtkKB) {
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        *reinterpret_cast<float4*>(sA + (fr + 32 * q) * kNtkLd + fc) = fa[q];
+        *reinterpret_cast<float4*>(sV + (vr + 8 * q) * kJvpLdV + vc) = fv[q];
+      }
+      __syncthreads();
+      if (k0 + kNtkKB < K) fetch(k0 + kNtkKB);
+#pragma unroll
+      for (int kk = 0; kk < kNtkKB; kk += 8) {
+        // as the Gram kernel: MFMA u contracts column kk + u (lh = 0) and kk + 4 + u (lh = 1) of X
+        // with the same rows of V; a lane's B operand is V[k][its column], one float
+        float4 av[2];
+        float bv[4][2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+          av[a] = *reinterpret_cast<const float4*>(sA + (wr + 32 * a + l32) * kNtkLd + kk + 4 * lh);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) bv[u][b] = sV[(kk + 4 * lh + u) * kJvpLdV + wc + 32 * b + l32];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+              const float x = u == 0 ? av[a].x : u == 1 ? av[a].y : u == 2 ? av[a].z : av[a].w;
+              g[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(x, bv[u][b], g[a][b], 0, 0, 0);
+            }
+      }
+    }
+    // C/D map: col = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int c = c0 + wc + 32 * b + l32;
+      const bool cok = c < Ky;
+      const float cv = (cvec && cok) ? cvec[c] : 0.f;
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        const int r0 = wr + 32 * a + 4 * lh;
+        const float* py = dY + (size_t)(I * tr + r0) * ldy + c;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int ro = (e & 3) + 8 * (e >> 2);
+          const float dy = (cok && r0 + ro < nval) ? py[(size_t)ro * ldy] : 0.f;
+          rs[a][e] = fmaf(g[a][b][e] + cv, dy, rs[a][e]);
+        }
+        // one accumulator's 16 loads in flight at a time: hoisting all 64 spilled
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+      sm[(wr + 32 * a + (e & 3) + 8 * (e >> 2) + 4 * lh) * kJvpLdR + (w & 1) * 32 + l32] = rs[a][e];
+  __syncthreads();
+  if (tid < kNtkTileRows) {
+    float s = 0.f;
+    for (int j = 0; j < 64; ++j) s += sm[tid * kJvpLdR + j];
+    srow[tid] = s;
+  }
+  __syncthreads();
+  const int wi = I * tw + tid;
+  if (tid < tw && wi < nwalk) {
+    float s = 0.f;
+    for (int i = 0; i < n; ++i) s += srow[tid * n + i];
+    part[(size_t)blockIdx.y * nwalk + wi] = s;
+  }
+}
+
+// jv[w] += sum_{cb < ncb} part[cb][w], cb ascending
+__global__ __launch_bounds__(256) void ntk_jvp_reduce_kernel(const float* __restrict__ part, int ncb, int nwalk,
+                                                             float* __restrict__ jv) {
+  const int wi = blockIdx.x * 256 + threadIdx.x;
+  if (wi >= nwalk) return;
+  float s = 0.f;
+  for (int cb = 0; cb < ncb; ++cb) s += part[(size_t)cb * nwalk + wi];
+  jv[wi] += s;
+}
+
+// cvec[c] = b[c] (null: 0) + sum_k m[k] V[k][c] (m null: the bias alone).  64 columns per
+// workgroup; wave q sums the rows k = q, q + 4, .. in ascending order (loads batched eight at a
+// time: one thread per column over all of K waited 100 us on its own load latencies), the four
+// partials are added in wave order
+__global__ __launch_bounds__(256) void ntk_jvp_cvec_kernel(const float* __restrict__ m, int K,
+                                                           const float* __restrict__ V, int ldv,
+                                                           const float* __restrict__ b, int Ky,
+                                                           float* __restrict__ cvec) {
+  __shared__ float red[4][64];
+  const int q = threadIdx.x >> 6, cl = threadIdx.x & 63, c = blockIdx.x * 64 + cl;
+  float s = 0.f;
+  if (m && c < Ky) {
+#pragma unroll 8
+    for (int k = q; k < K; k += 4) s = fmaf(m[k], V[(size_t)k * ldv + c], s);
+  }
+  red[q][cl] = s;
+  __syncthreads();
+  if (q == 0 && c < Ky) cvec[c] = (b ? b[c] : 0.f) + (((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl]);
+}
+
+// jv[w] += sum_{k < ka} J[w][k] va[k] + sum_{k < kb} J[w][ka + k] vb[k]: explicit per-walker
+// tangent rows against their two slices of the direction; one wave per walker, each lane's
+// columns in ascending order, then the butterfly
+__global__ __launch_bounds__(256) void ntk_rowdot_kernel(const float* __restrict__ J, int ldj,
+                                                         const float* __restrict__ va, int ka,
+                                                         const float* __restrict__ vb, int kb, int nwalk,
+                                                         float* __restrict__ jv) {
+  const int wi = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (wi >= nwalk) return;
+  const float* Jr = J + (size_t)wi * ldj;
+  float s = 0.f;
+  for (int k = lane; k < ka; k += 64) s = fmaf(Jr[k], va[k], s);
+  for (int k = lane; k < kb; k += 64) s = fmaf(Jr[ka + k], vb[k], s);
+  s = wave_sum(s);
+  if (lane == 0) jv[wi] += s;
 }
 
 // U[r][k] = X[r][k] - m[k] (row stride K) and a[r] = m . U[r] + (m . m + bias) / 2; one wave per row
@@ -366,6 +558,8 @@ __global__ __launch_bounds__(256) void minsr_matrix_kernel(const float* __restri
 
 int ntk_tile_walkers(int N) { return N >= 1 && N <= kNtkTileRows ? kNtkTileRows / N : 0; }
 
+int ntk_jvp_col_blocks(int Ky) { return (Ky + kJvpCols - 1) / kJvpCols; }
+
 void launch_ntk_gram(const float* X, int ldx, int Kx, const float* Y, int ldy, int Ky, const float* arow, int n,
                      int nwalk, int tw_own, int part, int nparts, float* T, hipStream_t s) {
   const int tw = ntk_tile_walkers(n);
@@ -386,6 +580,34 @@ void launch_ntk_centre(const float* X, int ldx, int K, const float* mean, bool b
                        hipStream_t s) {
   hipLaunchKernelGGL(ntk_centre_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, X, ldx, K, mean, bias ? 1.f : 0.f,
                      rows, U, a);
+}
+
+void launch_ntk_jvp(const float* X, int ldx, int K, const float* V, int ldv, const float* cvec, const float* dY,
+                    int ldy, int Ky, int n, int nwalk, float* part, float* jv, hipStream_t s) {
+  const int tw = ntk_tile_walkers(n);
+  if (tw < 1 || nwalk < 1 || K < 1 || Ky < 1) return;
+  const int nt = (nwalk + tw - 1) / tw, ncb = ntk_jvp_col_blocks(Ky);
+  auto vec_ok = [](const float* Z, int ld, int Kz) {
+    return Kz % 4 == 0 && ld % 4 == 0 && reinterpret_cast<uintptr_t>(Z) % 16 == 0;
+  };
+  if (vec_ok(X, ldx, K) && vec_ok(V, ldv, Ky))
+    hipLaunchKernelGGL(ntk_jvp_kernel<true>, dim3(nt, ncb), dim3(256), 0, s, X, ldx, K, V, ldv, cvec, dY, ldy, Ky, n,
+                       tw, nwalk, part);
+  else
+    hipLaunchKernelGGL(ntk_jvp_kernel<false>, dim3(nt, ncb), dim3(256), 0, s, X, ldx, K, V, ldv, cvec, dY, ldy, Ky, n,
+                       tw, nwalk, part);
+  hipLaunchKernelGGL(ntk_jvp_reduce_kernel, dim3((nwalk + 255) / 256), dim3(256), 0, s, part, ncb, nwalk, jv);
+}
+
+void launch_ntk_jvp_cvec(const float* mean, int K, const float* V, int ldv, const float* bias, int Ky, float* cvec,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(ntk_jvp_cvec_kernel, dim3((Ky + 63) / 64), dim3(256), 0, s, mean, K, V, ldv, bias, Ky, cvec);
+}
+
+void launch_ntk_rowdot(const float* J, int ldj, const float* va, int ka, const float* vb, int kb, int nwalk, float* jv,
+                       hipStream_t s) {
+  if (nwalk < 1) return;
+  hipLaunchKernelGGL(ntk_rowdot_kernel, dim3((nwalk + 3) / 4), dim3(256), 0, s, J, ldj, va, ka, vb, kb, nwalk, jv);
 }
 
 void launch_ntk_mirror(float* T, int B, hipStream_t s) {

@@ -481,6 +481,43 @@ class Psiformer:
                                      int(nparts), _stream(x.device)))
         return self.ntk_mirror(T) if mirror else T
 
+    # ---- SPRING (dh_ntk_jvp)
+    def _direction(self, v, device) -> torch.Tensor:
+        """``v`` as the flat float32 [nref] device buffer dh_ntk_jvp reads."""
+        flat = flat_params(self.spec, v, device) if isinstance(v, dict) else v
+        nref = ref_offsets(self.spec)[-1]
+        if not (torch.is_tensor(flat) and flat.dim() == 1 and flat.numel() == nref):
+            raise ValueError(f"the direction must be a ParamTree or a flat float32 [{nref}] tensor")
+        return flat.to(device=device, dtype=torch.float32).contiguous()
+
+    def ntk_jvp(self, params, data: torch.Tensor, ct: torch.Tensor, v, logpsi: torch.Tensor | None = None,
+                part: int = 0, nparts: int = 1, mirror: bool = True, want_T: bool = True):
+        """(T, jv) from one forward pass and one reverse walk (dh_ntk_jvp): T as ``ntk`` gives it
+        for the same arguments, bit for bit, and jv float32 [B], jv[b] = <g_b, v>, the per-walker
+        Jacobian-vector product with the direction ``v`` (a ParamTree or a flat float32 [nref]
+        device tensor in the ``params.flat`` layout).  jv is complete and identical on every
+        part; reproducible bit for bit; exactly 0 for a walker with non-finite log psi or zero
+        ``ct``.  ``want_T=False`` (``jvp``): no Gram products, T is None."""
+        h = self.prepare(params, data.device)
+        x = self._check_walkers(data)
+        B = x.shape[0]
+        ct = ct.to(device=x.device, dtype=torch.float32).contiguous()
+        if tuple(ct.shape) != (B, 2):
+            raise ValueError(f"cotangents must be [{B}, 2]")
+        vf = self._direction(v, x.device)
+        T = torch.empty(B, B, dtype=torch.float32, device=x.device) if want_T else None
+        jv = torch.empty(B, dtype=torch.float32, device=x.device)
+        ws = h.workspace(max(h.lib.dh_ntk_jvp_workspace_bytes(h.h, B), 1))
+        _lib.check(h.lib.dh_ntk_jvp(h.h, _ptr(x), B, _ptr(ct), _ptr(vf), _ptr(T), _ptr(jv), _ptr(logpsi), _ptr(ws),
+                                    ws.numel(), int(part), int(nparts), _stream(x.device)))
+        if want_T and mirror:
+            self.ntk_mirror(T)
+        return T, jv
+
+    def jvp(self, params, data: torch.Tensor, ct: torch.Tensor, v, logpsi: torch.Tensor | None = None) -> torch.Tensor:
+        """jv[b] = <g_b, v>, float32 [B]: ``ntk_jvp`` without the Gram matrix."""
+        return self.ntk_jvp(params, data, ct, v, logpsi=logpsi, want_T=False)[1]
+
     # ---- KFAC (optimizers/kfac.py:195-241; dh_kfac_*)
     def kfac_layout(self, device) -> dict:
         """dh_kfac_layout: statistics size, factor slots and dense blocks."""

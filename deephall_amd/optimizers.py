@@ -16,6 +16,9 @@ space: the per-walker gradient Gram matrix comes from the dh_ntk kernels, the 2B
 is float64 torch.linalg on the device, the update direction one more dh_logpsi_vjp.  Across
 ranks (``optim.minsr.sharded``) every rank computes its share of the Gram matrix of the gathered
 walkers (dh_ntk_part) and the solve matrix comes from one kernel (dh_minsr_matrix).
+``optim.minsr.momentum`` turns the step into SPRING: the same solve with the previous direction's
+per-walker Jacobian-vector products (dh_ntk_jvp, in the Gram matrix's reverse walk) on its
+right-hand side.
 """
 
 from __future__ import annotations
@@ -146,19 +149,30 @@ def make_kfac_training_step(cfg: Config, network):
 
 class MinsrState:
     """MinSR keeps no curvature or momentum between steps: the step counter (the learning-rate
-    schedule's argument) is the whole state."""
+    schedule's argument) is the whole state.  SPRING (``optim.minsr.momentum`` > 0) adds ``prev``,
+    the previous step's unscaled direction phi, float32 [nref] on the device."""
 
-    def __init__(self):
+    def __init__(self, prev: torch.Tensor | None = None):
         self.step = 0
+        self.prev = prev
 
     def state_dict(self):
-        return {"step": self.step}
+        if self.prev is None:
+            return {"step": self.step}
+        return {"step": self.step, "prev": self.prev}
 
     def load_state_dict(self, d):
         self.step = int(d["step"])
+        if self.prev is not None:
+            self.prev.copy_(torch.as_tensor(d["prev"]))
 
 
-def minsr_direction(net, params: ParamTree, data: torch.Tensor, diff: torch.Tensor, damping: float) -> ParamTree:
+def _flat_direction(prev):
+    return prev.flat if hasattr(prev, "flat") else prev
+
+
+def minsr_direction(net, params: ParamTree, data: torch.Tensor, diff: torch.Tensor, damping: float,
+                    prev=None, momentum: float = 0.0) -> ParamTree:
     """The linear-algebra half of a MinSR step for given clipped energy differences ``diff``
     [B, 2] float32 (re, im; NaN = walker dropped):
 
@@ -168,14 +182,29 @@ def minsr_direction(net, params: ParamTree, data: torch.Tensor, diff: torch.Tens
     walkers v (non-NaN diff, finite log psi; n of them) and divided by sqrt(n); eps~ =
     [Re diff; Im diff] / sqrt(n), zero outside v.  O~ O~^T is the centred dh_ntk Gram matrix of
     [data; data] with cotangents (1, 0) | (0, 1); the solve runs in float64 on the device; the
-    product with O~^T is dh_logpsi_vjp with the solution as cotangents."""
+    product with O~^T is dh_logpsi_vjp with the solution as cotangents.
+
+    SPRING (``prev`` = the previous direction phi_prev, a ParamTree or a flat [nref] tensor, and
+    ``momentum`` = mu != 0): the damping pulls towards mu phi_prev instead of towards 0,
+
+        phi = mu phi_prev + 2 O~^T (O~ O~^T + damping I)^-1 (eps~ - (mu / 2) O~ phi_prev)
+            = (O~^T O~ + damping I)^-1 (2 O~^T eps~ + damping mu phi_prev)
+
+    with O~ phi_prev = C jv / sqrt(n), jv the per-walker Jacobian-vector products that come out of
+    the Gram matrix's own reverse walk (``net.ntk_jvp``, dh_ntk_jvp), taken to float64; the matrix
+    is then dh_minsr_matrix's on the device.  Without ``prev`` or with mu = 0 this is the MinSR
+    path above, bit for bit."""
     B = data.shape[0]
     dev = data.device
+    spring = prev is not None and momentum != 0
     ct = torch.zeros(2 * B, 2, dtype=torch.float32, device=dev)
     ct[:B, 0] = 1.0
     ct[B:, 1] = 1.0
     lp = torch.empty(2 * B, 2, dtype=torch.float32, device=dev)
-    T = net.ntk(params, torch.cat([data, data]), ct, logpsi=lp).double()
+    if spring:
+        T, jv = net.ntk_jvp(params, torch.cat([data, data]), ct, _flat_direction(prev), logpsi=lp)
+    else:
+        T = net.ntk(params, torch.cat([data, data]), ct, logpsi=lp)
     diff = diff.to(device=dev, dtype=torch.float64)
     valid = ~torch.isnan(diff).any(dim=1) & torch.isfinite(lp[:B]).all(dim=1)
     v = valid.double()
@@ -185,18 +214,27 @@ def minsr_direction(net, params: ParamTree, data: torch.Tensor, diff: torch.Tens
         a = a * v
         return a - v * (a.sum(-1, keepdim=True) / n)
 
-    T4 = centre(T.view(2, B, 2, B))                              # columns
-    T4 = centre(T4.permute(2, 3, 0, 1)).permute(2, 3, 0, 1)      # rows
-    Tbar = T4.reshape(2 * B, 2 * B) / n
+    if spring and T.is_cuda:
+        A = minsr_matrix(T, valid, damping)
+    else:
+        T = T.double()
+        T4 = centre(T.view(2, B, 2, B))                              # columns
+        T4 = centre(T4.permute(2, 3, 0, 1)).permute(2, 3, 0, 1)      # rows
+        Tbar = T4.reshape(2 * B, 2 * B) / n
+        A = Tbar + float(damping) * torch.eye(2 * B, dtype=torch.float64, device=dev)
     eps = (torch.nan_to_num(diff, nan=0.0) * v[:, None]).t().reshape(2 * B) / n.sqrt()
-    A = Tbar + float(damping) * torch.eye(2 * B, dtype=torch.float64, device=dev)
+    if spring:
+        eps = eps - (0.5 * float(momentum)) * centre(jv.double().view(2, B)).reshape(2 * B) / n.sqrt()
     L, info = torch.linalg.cholesky_ex(A)
     if int(info) == 0:
         y = torch.cholesky_solve(eps[:, None], L)[:, 0]
     else:
         y = torch.linalg.solve(A, eps)
     ct2 = (2.0 * centre(y.view(2, B)) / n.sqrt()).t().contiguous().float()
-    return net.vjp(params, data, ct2)
+    delta = net.vjp(params, data, ct2)
+    if spring:
+        delta.flat.add_(_flat_direction(prev).to(delta.flat.dtype), alpha=float(momentum))
+    return delta
 
 
 def minsr_matrix(T: torch.Tensor, valid: torch.Tensor, damping: float) -> torch.Tensor:
@@ -221,7 +259,7 @@ def minsr_matrix(T: torch.Tensor, valid: torch.Tensor, damping: float) -> torch.
 
 
 def minsr_direction_sharded(net, params: ParamTree, data: torch.Tensor, diff: torch.Tensor, damping: float,
-                            keep: dict | None = None) -> ParamTree:
+                            keep: dict | None = None, prev=None, momentum: float = 0.0) -> ParamTree:
     """``minsr_direction`` over the walkers of every rank: ``data`` [B, N, 2] and
     ``diff`` [B, 2] are this rank's shard, the direction is that of the gathered batch of
     B_g = world size x B walkers, identical on every rank.
@@ -233,7 +271,12 @@ def minsr_direction_sharded(net, params: ParamTree, data: torch.Tensor, diff: to
     on every rank.  The centred solution's slice for this rank's walkers goes through
     dh_logpsi_vjp; the all-reduce SUM of the results is the direction.  World size 1: the same
     kernels, no collectives.  Shards must be equal (``ValueError``).
-    ``keep``: a dict that receives T, A and the solution y (tests)."""
+    ``keep``: a dict that receives T, A and the solution y (tests).
+    ``prev``, ``momentum``: SPRING, as in ``minsr_direction``.  jv over all 2 B_g walkers comes out
+    of the same dh_ntk_jvp(part = rank, nparts = R) call complete and identical on every rank, and
+    phi_prev is identical on every rank because the direction is: no further collective.  ``keep``
+    then receives jv as well."""
+    spring = prev is not None and momentum != 0
     R, rank = constants.world_size(), constants.rank()
     B = data.shape[0]
     dev = data.device
@@ -257,7 +300,11 @@ def minsr_direction_sharded(net, params: ParamTree, data: torch.Tensor, diff: to
     ct[:Bg, 0] = 1.0
     ct[Bg:, 1] = 1.0
     lp = torch.empty(2 * Bg, 2, dtype=torch.float32, device=dev)
-    T = net.ntk(params, torch.cat([data_g, data_g]), ct, logpsi=lp, part=rank, nparts=R, mirror=False)
+    if spring:
+        T, jv = net.ntk_jvp(params, torch.cat([data_g, data_g]), ct, _flat_direction(prev), logpsi=lp, part=rank,
+                            nparts=R, mirror=False)
+    else:
+        T = net.ntk(params, torch.cat([data_g, data_g]), ct, logpsi=lp, part=rank, nparts=R, mirror=False)
     if R > 1:
         dist.all_reduce(T)
     net.ntk_mirror(T)
@@ -270,6 +317,12 @@ def minsr_direction_sharded(net, params: ParamTree, data: torch.Tensor, diff: to
     v = valid.double()
     n = v.sum().clamp(min=1.0)
     eps = (torch.nan_to_num(diff_g, nan=0.0) * v[:, None]).t().reshape(2 * Bg) / n.sqrt()
+    if spring:
+        j2 = jv.double().view(2, Bg) * v
+        j2 = j2 - v * (j2.sum(-1, keepdim=True) / n)
+        eps = eps - (0.5 * float(momentum)) * j2.reshape(2 * Bg) / n.sqrt()
+        if keep is not None:
+            keep["jv"] = jv
     L, info = torch.linalg.cholesky_ex(A)
     if int(info) == 0:
         y = torch.cholesky_solve(eps[:, None], L)[:, 0]
@@ -284,6 +337,8 @@ def minsr_direction_sharded(net, params: ParamTree, data: torch.Tensor, diff: to
     delta = net.vjp(params, data, ct2)
     if R > 1:
         dist.all_reduce(delta.flat)  # a sum: every row carries the global 1 / sqrt(n)
+    if spring:
+        delta.flat.add_(_flat_direction(prev).to(delta.flat.dtype), alpha=float(momentum))
     return delta
 
 
@@ -293,7 +348,13 @@ def make_minsr_training_step(cfg: Config, network):
     KFAC approximates — then KFAC's norm constraint against the ENERGY_GRAD gradient g:
     c = min(1, sqrt(norm_constraint / (lr^2 <delta, g>))), params -= lr c delta.
     ``optim.minsr.sharded``: the direction over the walkers of every rank
-    (minsr_direction_sharded) and g averaged over ranks as the Adam step's."""
+    (minsr_direction_sharded) and g averaged over ranks as the Adam step's.
+    ``optim.minsr.momentum`` = mu > 0: SPRING (Goldshlager, Abrahamsen, Lin 2024), delta = phi of
+    ``minsr_direction`` with the previous step's phi — unscaled by lr and c, non-finite entries
+    zeroed — kept in the state; the first step's phi_prev is 0."""
+    mu = float(cfg.optim.minsr.momentum)
+    if not 0.0 <= mu < 1.0:
+        raise ValueError(f"optim.minsr.momentum must be in [0, 1), got {mu}")
     sharded = bool(cfg.optim.minsr.sharded)
     if constants.world_size() > 1 and not sharded:
         raise NotImplementedError("MinSR on more than one rank needs each rank to compute a share of the gathered "
@@ -306,8 +367,8 @@ def make_minsr_training_step(cfg: Config, network):
     opt = cfg.optim.minsr
 
     def init(params, key=None, data=None):
-        del params, key, data
-        return MinsrState()
+        del key, data
+        return MinsrState(torch.zeros_like(params.flat) if mu > 0 else None)
 
     def step(state: CheckpointState, key=None, **stat_kw):
         params, data, opt_state, width = state
@@ -317,11 +378,13 @@ def make_minsr_training_step(cfg: Config, network):
         grad = net.vjp(params, data, grad_cotangent(diff, nvalid, 0))
         if sharded:
             constants.pmean_(grad.flat)
-            delta = minsr_direction_sharded(net, params, data, diff, opt.damping)
+            delta = minsr_direction_sharded(net, params, data, diff, opt.damping, prev=opt_state.prev, momentum=mu)
         else:
-            delta = minsr_direction(net, params, data, diff, opt.damping)
+            delta = minsr_direction(net, params, data, diff, opt.damping, prev=opt_state.prev, momentum=mu)
         lr = lr_schedule(opt.lr, opt_state.step)
         d = torch.nan_to_num(delta.flat, nan=0.0, posinf=0.0, neginf=0.0)
+        if opt_state.prev is not None:
+            opt_state.prev.copy_(d)
         sq = (lr * lr) * torch.dot(d.double(), torch.nan_to_num(grad.flat).double())
         c = torch.where(sq > opt.norm_constraint, torch.sqrt(opt.norm_constraint / sq.clamp(min=1e-300)),
                         torch.ones_like(sq))

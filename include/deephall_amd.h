@@ -215,7 +215,24 @@ int dh_kfac_step(dh_handle* h, float* raw, const float* stats, float ema, float 
  *   the assembly); no atomics: two calls give identical bits; A is exactly symmetric; an invalid
  *   walker's rows and columns are 0 with damping on the diagonal.  ws: 8-byte aligned device
  *   memory of dh_minsr_matrix_workspace_bytes(Bg); a null pointer is DH_EINVAL, a short workspace
- *   DH_ENOMEM, both before any device call. */
+ *   DH_ENOMEM, both before any device call.
+ *
+ * dh_ntk_jvp: the per-walker Jacobian-vector product jv[b] = <g_b, v>, float32 [B], WRITTEN, for
+ *   a parameter direction v (float32, dh_ref_layout, device), in the same forward pass and
+ *   reverse walk as dh_ntk_part and with its arguments: every dense map adds
+ *   sum_{t in b} (x_t V + v_b) . dy_t for its slices V, v_b of v (exact-f32 MFMA on the
+ *   batch-mean-centred rows, ntk.hip), the LayerNorm and Jastrow parameters their explicit rows'
+ *   dot products.  T non-null: exactly what dh_ntk_part(part, nparts) writes (not mirrored).
+ *   T null: no Gram products (needs part 0 of 1, else DH_EINVAL).  jv is complete for every
+ *   walker on every part and does not depend on T or the part; no atomics, two calls give
+ *   identical bits, and a power-of-two multiple of v gives that multiple of jv bit for bit.  A
+ *   walker whose log psi is not finite, or whose ct is zero, gets jv = 0 exactly.  Handles and
+ *   states refused as by dh_ntk; a null v or jv is DH_EINVAL; ws_bytes <
+ *   dh_ntk_jvp_workspace_bytes(h, B) (>= dh_ntk_workspace_bytes) is DH_ENOMEM; every check
+ *   precedes the first device call. */
+size_t dh_ntk_jvp_workspace_bytes(const dh_handle* h, int batch);
+int dh_ntk_jvp(dh_handle* h, const float* x, int B, const float* ct, const float* v, float* T, float* jv,
+               float* logpsi, void* ws, size_t ws_bytes, int part, int nparts, void* stream);
 size_t dh_ntk_workspace_bytes(const dh_handle* h, int batch);
 int dh_ntk_tile_walkers(const dh_handle* h);
 int dh_ntk(dh_handle* h, const float* x, int B, const float* ct, float* T, float* logpsi, void* ws, size_t ws_bytes,

@@ -15,7 +15,9 @@ matrix peak.
 (the same work as dh_ntk), dh_ntk_part(p of R) for every p on this one GPU — the slowest against
 1 / R of the whole — and dh_minsr_matrix against the float64 torch assembly of
 optimizers.minsr_direction and against its traffic of 16 M^2 bytes (T read twice, A written once).
-usage: ntk_bench.py [B] [NSPINS FLUX] [reps] [--parts R]..."""
+``--jvp`` also times SPRING's call: dh_ntk_jvp with T against dh_ntk_part(0 of 1), dh_ntk_jvp
+without T against dh_logpsi_vjp, and the JVP's 2 R P FLOP over the differences.
+usage: ntk_bench.py [B] [NSPINS FLUX] [reps] [--parts R]... [--jvp]"""
 import statistics
 import sys
 from pathlib import Path
@@ -30,6 +32,9 @@ from deephall_amd.train import init_guess  # noqa: E402
 
 PEAK_F32_MATRIX = 157.3e12
 
+want_jvp = "--jvp" in sys.argv
+if want_jvp:
+    sys.argv.remove("--jvp")
 parts_list = []
 while "--parts" in sys.argv:
     i = sys.argv.index("--parts")
@@ -85,6 +90,27 @@ print(f"Gram FLOP / whole call: {whole / 1e12:6.1f} TF/s = {whole / PEAK_F32_MAT
 if ntk[0] > vjp[0]:
     net = flop / ((ntk[0] - vjp[0]) * 1e-3)
     print(f"Gram FLOP / (call - VJP): {net / 1e12:6.1f} TF/s = {net / PEAK_F32_MATRIX:.3f} of peak")
+
+if want_jvp:
+    # SPRING's call: dh_ntk_jvp (T and jv in one reverse walk) against dh_ntk_part(0 of 1), the same
+    # Gram work without the direction; the JVP-only call against dh_logpsi_vjp
+    v = torch.randn_like(params.flat)
+    nparam = sum(int(p.numel()) for p in params.values())
+    jflop = 2.0 * R * nparam
+    part = timed(lambda: model.ntk(params, x2, ct, part=0, nparts=1, mirror=False))
+    both = timed(lambda: model.ntk_jvp(params, x2, ct, v, mirror=False))
+    only = timed(lambda: model.jvp(params, x2, ct, v))
+    print(f"dh_ntk_part(0 of 1) {part[0]:9.2f} ms  (min {part[1]:.2f}, max {part[2]:.2f})")
+    print(f"dh_ntk_jvp (with T) {both[0]:9.2f} ms  (min {both[1]:.2f}, max {both[2]:.2f}): {both[0] / part[0]:.4f} of "
+          f"dh_ntk_part(0 of 1)")
+    print(f"dh_ntk_jvp (T null) {only[0]:9.2f} ms  (min {only[1]:.2f}, max {only[2]:.2f}); "
+          f"dh_logpsi_vjp {vjp[0]:.2f} ms")
+    print(f"JVP FLOP = 2 R P = {jflop:.3e} (P = {nparam})")
+    for label, dt in (("(with T) - dh_ntk_part", both[0] - part[0]), ("(T null) - dh_logpsi_vjp", only[0] - vjp[0])):
+        if dt > 0:
+            rate = jflop / (dt * 1e-3)
+            print(f"JVP FLOP / ({label} = {dt:.2f} ms): {rate / 1e12:6.1f} TF/s = {rate / PEAK_F32_MATRIX:.3f} of peak "
+                  f"(the difference also holds the packing, cvec and row-dot launches)")
 
 if parts_list:
     from deephall_amd.optimizers import minsr_matrix  # noqa: E402
