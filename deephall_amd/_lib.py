@@ -34,6 +34,7 @@ STAT_NAMES = [
 
 EXPORTS = [
     "dh_create",
+    "dh_create_cf",
     "dh_destroy",
     "dh_last_error",
     "dh_version",
@@ -140,6 +141,8 @@ def load(path: Path | str | None = None):
     vp, sz, i32, u64, i64 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_int64
     lib.dh_create.argtypes = [C.POINTER(DhConfig), C.POINTER(vp)]
     lib.dh_create.restype = i32
+    lib.dh_create_cf.argtypes = [C.POINTER(DhConfig), C.POINTER(C.c_int), i32, C.POINTER(vp)]
+    lib.dh_create_cf.restype = i32
     lib.dh_destroy.argtypes = [vp]
     lib.dh_destroy.restype = None
     lib.dh_last_error.restype = C.c_char_p

@@ -42,6 +42,7 @@ class InteractionType(str, enum.Enum):
 class NetworkType(str, enum.Enum):
     psiformer = "psiformer"
     laughlin = "laughlin"
+    jain = "jain"
 
 
 class OrbitalType(str, enum.Enum):
@@ -70,10 +71,26 @@ class PsiformerNetwork:
 
 
 @dataclass
+class JainNetwork:
+    """Jain composite-fermion state with two Lambda levels (not in the reference; networks/jain.py).
+    ``cf_flux``: p, 2p vortices per electron.  ``occupation``: N pairs (n, m), Lambda level n in
+    {0, 1} and |m| <= Q1 + n, one determinant column each; None is the ground state with both
+    levels filled (N = 4 Q1 + 4)."""
+
+    cf_flux: int = 1
+    occupation: Optional[tuple] = None
+
+    def __post_init__(self):
+        if self.occupation is not None:  # a list of [n, m] lists from a config file
+            self.occupation = tuple((int(n), float(m)) for n, m in self.occupation)
+
+
+@dataclass
 class Network:
     type: NetworkType = NetworkType.psiformer
     orbital: OrbitalType = OrbitalType.full
     psiformer: PsiformerNetwork = field(default_factory=PsiformerNetwork)
+    jain: JainNetwork = field(default_factory=JainNetwork)
 
 
 @dataclass

@@ -154,7 +154,9 @@ struct dh_handle {
   bool params_set = false;
   bool ref_set = false;
   bool laughlin = false;          // DH_NETWORK_LAUGHLIN: no parameters, laughlin.hip kernels
-  std::vector<int> expo_host;     // Laughlin exponents [2][N] = (Q1 + m_j, Q1 - m_j)
+  bool jain = false;              // DH_NETWORK_JAIN: a laughlin handle whose kernels are cf.hip's
+  int cf_dense = 0;               // its number of level-1 (dense) columns
+  std::vector<int> expo_host;     // Laughlin exponents [2][N] = (Q1 + m_j, Q1 - m_j); Jain: cf.hip's column table
   int* expo = nullptr;            // device copy (uploaded at first use)
   KfacHost* kfac = nullptr;       // KFAC plan (built at first dh_kfac_* call)
   Profiler prof;
@@ -231,7 +233,112 @@ int laughlin_exponents(const dh_config* cfg, std::vector<int>& ex) {
     return fail(DH_EINVAL, "Laughlin: N too large for the one-workgroup kernel's LDS (160 KiB)");
   return DH_OK;
 }
+// The handle of a parameter-free analytic state (Laughlin, Jain): no network dimensions
+dh_handle* analytic_handle(const dh_config* cfg, const std::vector<int>& ex) {
+  const int N = cfg->n_up + cfg->n_dn;
+  auto* h = new dh_handle();
+  h->cfg = *cfg;
+  h->laughlin = true;
+  h->expo_host = ex;
+  Dims& d = h->d;
+  d = Dims{};
+  d.N = N;
+  d.n_up = cfg->n_up;
+  d.n_dn = cfg->n_dn;
+  d.T = 2 * N;
+  d.C = 2 * N + 5;
+  d.M = 1;
+  d.Q = 0.5f * cfg->flux;
+  d.r = cfg->radius > 0.f ? cfg->radius : std::sqrt(d.Q);
+  d.H = 1;
+  d.dh = 4;
+  d.D = 4;
+  d.L = 0;
+  d.K = 1;
+  d.NB = 1;
+  d.orb_cols = 0;
+  d.ld_orb = 0;
+  d.interaction = cfg->interaction_type;
+  d.lambda = cfg->interaction_strength;
+  h->offsets = {0};
+  h->ref_offsets = {0};
+  h->params_set = h->ref_set = true;  // nothing to upload
+  return h;
+}
+
+// Jain state with two Lambda levels (cf.hip).  occ: [n_occ][2] = (level, 2 m), or null for the
+// ground state with both levels filled (N = 4 Q1 + 4: all of level 0, then all of level 1, m
+// ascending).  Fills the kernel's column table.
+int jain_table(const dh_config* cfg, const int* occ, int n_occ, std::vector<int>& tab, int& n_dense) {
+  const int N = cfg->n_up + cfg->n_dn;
+  const int p = cfg->cf_flux < 1 ? 1 : cfg->cf_flux;
+  const int q2 = cfg->flux - 2 * p * (N - 1);  // 2 Q1
+  if (q2 < 0) return fail(DH_EINVAL, "Jain: flux too small for N electrons (Q1 < 0)");
+  std::vector<int> lev, m2;
+  if (!occ) {
+    if (N != 2 * q2 + 4)
+      return fail(DH_EINVAL, "Jain: no ground state of two filled levels at this filling (needs N = 4 Q1 + 4)");
+    for (int n = 0; n < 2; ++n)
+      for (int m = -q2 - 2 * n; m <= q2 + 2 * n; m += 2) {
+        lev.push_back(n);
+        m2.push_back(m);
+      }
+  } else {
+    if (n_occ != N) return fail(DH_EINVAL, "Jain: the occupation needs one orbital per electron (n_occ = N)");
+    for (int j = 0; j < N; ++j) {
+      const int n = occ[2 * j], m = occ[2 * j + 1];
+      if (n != 0 && n != 1) return fail(DH_EINVAL, "Jain: Lambda level must be 0 or 1");
+      if (((m - q2) % 2) != 0) return fail(DH_EINVAL, "Jain: 2 m must have the parity of 2 Q1");
+      if (std::abs(m) > q2 + 2 * n) return fail(DH_EINVAL, "Jain: |m| > Q1 + level");
+      for (int k = 0; k < j; ++k)
+        if (lev[k] == n && m2[k] == m) return fail(DH_EINVAL, "Jain: orbital occupied twice");
+      lev.push_back(n);
+      m2.push_back(m);
+    }
+  }
+  n_dense = 0;
+  tab.assign(3 * N + 2, 0);
+  for (int j = 0; j < N; ++j) {
+    tab[3 * j] = lev[j];
+    tab[3 * j + 1] = (q2 + m2[j]) / 2;  // A >= -1
+    tab[3 * j + 2] = (q2 - m2[j]) / 2;  // B >= -1
+    if (lev[j]) {
+      tab.push_back(j);
+      ++n_dense;
+    }
+  }
+  tab[3 * N] = n_dense;
+  tab[3 * N + 1] = p;
+  if (cf_smem_bytes(N, n_dense, true) > 160 * 1024)
+    return fail(DH_EINVAL, "Jain: N and the number of level-1 orbitals need " +
+                               std::to_string(cf_smem_bytes(N, n_dense, true)) +
+                               " bytes of LDS; the one-workgroup kernel has 160 KiB");
+  return DH_OK;
+}
+
+int create_jain(const dh_config* cfg, const int* occ, int n_occ, dh_handle** out) {
+  const int N = cfg->n_up + cfg->n_dn;
+  if (cfg->n_up < 0 || cfg->n_dn < 0 || N < 1 || N > 32) return fail(DH_EINVAL, "Jain: need 1 <= N <= 32 electrons");
+  if (cfg->flux < 1 || cfg->flux > 126) return fail(DH_EINVAL, "Jain needs 1 <= flux <= 126");
+  if (cfg->interaction_type != DH_INTERACTION_COULOMB && cfg->interaction_type != DH_INTERACTION_HARMONIC)
+    return fail(DH_EINVAL, "Jain: bad interaction type");
+  std::vector<int> tab;
+  int n_dense = 0;
+  if (int rc = jain_table(cfg, occ, n_occ, tab, n_dense)) return rc;
+  dh_handle* h = analytic_handle(cfg, tab);
+  h->jain = true;
+  h->cf_dense = n_dense;
+  *out = h;
+  return DH_OK;
+}
 }  // namespace
+
+int dh_create_cf(const dh_config* cfg, const int* occ, int n_occ, dh_handle** out) {
+  if (!cfg || !out || !occ) return fail(DH_EINVAL, "null argument");
+  if (cfg->struct_size != sizeof(dh_config)) return fail(DH_EINVAL, "dh_config.struct_size must equal sizeof(dh_config)");
+  if (cfg->network_type != DH_NETWORK_JAIN) return fail(DH_EINVAL, "Jain: dh_create_cf needs network_type DH_NETWORK_JAIN");
+  return create_jain(cfg, occ, n_occ, out);
+}
 
 int dh_create(const dh_config* cfg, dh_handle** out) {
   if (!cfg || !out) return fail(DH_EINVAL, "null argument");
@@ -246,36 +353,10 @@ int dh_create(const dh_config* cfg, dh_handle** out) {
       return fail(DH_EINVAL, "bad interaction type");
     std::vector<int> ex;
     if (int rc = laughlin_exponents(cfg, ex)) return rc;
-    auto* h = new dh_handle();
-    h->cfg = *cfg;
-    h->laughlin = true;
-    h->expo_host = ex;
-    Dims& d = h->d;
-    d = Dims{};
-    d.N = N;
-    d.n_up = cfg->n_up;
-    d.n_dn = cfg->n_dn;
-    d.T = 2 * N;
-    d.C = 2 * N + 5;
-    d.M = 1;
-    d.Q = 0.5f * cfg->flux;
-    d.r = cfg->radius > 0.f ? cfg->radius : std::sqrt(d.Q);
-    d.H = 1;
-    d.dh = 4;
-    d.D = 4;
-    d.L = 0;
-    d.K = 1;
-    d.NB = 1;
-    d.orb_cols = 0;
-    d.ld_orb = 0;
-    d.interaction = cfg->interaction_type;
-    d.lambda = cfg->interaction_strength;
-    h->offsets = {0};
-    h->ref_offsets = {0};
-    h->params_set = h->ref_set = true;  // nothing to upload
-    *out = h;
+    *out = analytic_handle(cfg, ex);
     return DH_OK;
   }
+  if (cfg->network_type == DH_NETWORK_JAIN) return create_jain(cfg, nullptr, 0, out);
   if (cfg->network_type != DH_NETWORK_PSIFORMER) return fail(DH_EINVAL, "bad network type");
   const int N = cfg->n_up + cfg->n_dn;
   if (cfg->n_up < 0 || cfg->n_dn < 0 || N < 1 || N > 32) return fail(DH_EINVAL, "need 1 <= N <= 32 electrons");
@@ -862,7 +943,10 @@ int value_pass(dh_handle* h, const float* x, int nw, const Work& w, float* logps
   if (h->laughlin) {
     if (int rc = ensure_expo(h)) return rc;
     PROF(PK_DET_VALUE, 0.0, 8.0 * nw * h->d.N);
-    launch_laughlin(h->d, x, h->expo, logpsi, nullptr, nullptr, nw, s);
+    if (h->jain)
+      launch_cf(h->d, x, h->expo, h->cf_dense, logpsi, nullptr, nullptr, nw, s);
+    else
+      launch_laughlin(h->d, x, h->expo, logpsi, nullptr, nullptr, nw, s);
     return check_launch();
   }
   if (int rc = run_trunk(h, x, nw, 1, w, s, geo_ready)) return rc;
@@ -961,7 +1045,10 @@ int dh_local_energy(dh_handle* h, const float* x, int B, float* e_l, float* obs,
     if (int rc = ensure_expo(h)) return rc;
     hipStream_t s = (hipStream_t)stream;
     PROF(PK_DET_ENERGY, 0.0, 48.0 * B);
-    launch_laughlin(d, x, h->expo, nullptr, e_l, obs, B, s);
+    if (h->jain)
+      launch_cf(d, x, h->expo, h->cf_dense, nullptr, e_l, obs, B, s);
+    else
+      launch_laughlin(d, x, h->expo, nullptr, e_l, obs, B, s);
     return check_launch();
   }
   // largest chunk that fits the workspace

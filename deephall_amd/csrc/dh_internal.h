@@ -388,6 +388,13 @@ size_t laughlin_smem_bytes(int N);
 void launch_laughlin(const Dims& d, const float* x, const int* expo, float* logpsi, float* e_l, float* obs, int nw,
                      hipStream_t s);
 
+// cf.hip: the same two launches for a Jain state with two Lambda levels.  tab: per column
+// (level, A = Q1 + m, B = Q1 - m), then the number of level-1 columns n_dense, p, and the
+// column of each of them.  LDS per walker by instantiation.
+size_t cf_smem_bytes(int N, int n_dense, bool energy);
+void launch_cf(const Dims& d, const float* x, const int* tab, int n_dense, float* logpsi, float* e_l, float* obs,
+               int nw, hipStream_t s);
+
 // det.hip: backward of log psi = J + log sum_k det Phi_k for per-walker cotangents ct[nw][2]:
 // dF [nw*N][ld_orb] (all columns written) and jg[nw][2] = ct.re * dJ / d(ee_par, ee_anti)
 void launch_det_bwd(const Dims& d, const float* F, const float* x, const float* jastrow, const float* norm,

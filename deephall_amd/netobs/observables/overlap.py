@@ -1,8 +1,9 @@
 """overlap.py:24-70: overlap |<Laughlin|psi>|^2 from the ratio phi_L / psi on psi's walkers.
 
 Both log-amplitudes are native (``dh_logpsi`` of the network and of the Laughlin state of
-the same system); ratio = exp(log phi - log psi - shift), shift = the walker mean of
-log phi - log psi; digest: |nanmean(ratio)|^2 / nanmean(|ratio|^2) over the steps.
+the same system, or of the Jain state ``network.jain`` describes with
+``estimator_options["reference"] = "jain"``); ratio = exp(log phi - log psi - shift),
+shift = the walker mean of log phi - log psi; digest: |nanmean(ratio)|^2 / nanmean(|ratio|^2) over the steps.
 """
 
 from __future__ import annotations
@@ -27,7 +28,10 @@ class OverlapEstimator(Estimator):
     def __init__(self, adaptor, system, estimator_options, observable_options):
         super().__init__(adaptor, system, estimator_options, observable_options)
         cfg = adaptor.cfg
-        self.laughlin = make_network(cfg.system, dataclasses.replace(cfg.network, type=NetworkType.laughlin))
+        reference = str((estimator_options or {}).get("reference", "laughlin"))
+        if reference not in ("laughlin", "jain"):
+            raise ValueError(f"overlap: reference must be 'laughlin' or 'jain', got {reference!r}")
+        self.laughlin = make_network(cfg.system, dataclasses.replace(cfg.network, type=NetworkType(reference)))
 
     def empty_val_state(self, steps: int):
         return {"ratio": torch.zeros(steps, dtype=torch.complex64), "ratio_square": torch.zeros(steps)}, {}

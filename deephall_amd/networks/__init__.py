@@ -3,6 +3,7 @@
 from __future__ import annotations
 
 from ..config import Network, NetworkType, System
+from .jain import Jain, JainCallable
 from .laughlin import Laughlin, LaughlinQuasiparticle
 from .psiformer import Psiformer
 
@@ -13,6 +14,9 @@ def make_network(system: System, network: Network) -> Psiformer:
     if ntype == NetworkType.laughlin.value:  # networks/__init__.py:24-27 (ground state, quasihole and
         # quasiparticle fillings all run on laughlin.hip)
         return Laughlin(flux=system.flux, nspins=system.nspins, excitation_lz=system.lz_center, system=system)
+    if ntype == NetworkType.jain.value:  # cf.hip; occupation None: both Lambda levels filled
+        return Jain(flux=system.flux, nspins=system.nspins, cf_flux=network.jain.cf_flux,
+                    occupation=network.jain.occupation, system=system)
     if ntype == NetworkType.psiformer.value:
         return Psiformer(
             Q=Q,
@@ -27,4 +31,4 @@ def make_network(system: System, network: Network) -> Psiformer:
     raise ValueError(f"unknown network type {network.type}")
 
 
-__all__ = ["make_network", "Psiformer", "Laughlin", "LaughlinQuasiparticle"]
+__all__ = ["make_network", "Psiformer", "Laughlin", "LaughlinQuasiparticle", "Jain", "JainCallable"]

@@ -54,6 +54,8 @@ extern "C" {
 #define DH_INTERACTION_HARMONIC 1
 #define DH_NETWORK_PSIFORMER 0
 #define DH_NETWORK_LAUGHLIN 1 /* networks/laughlin.py: ground state, quasihole, quasiparticle (no parameters) */
+#define DH_NETWORK_JAIN 2 /* Jain composite-fermion state, two Lambda levels (no parameters): dh_create builds the
+                            filled-levels ground state N = 4 Q1 + 4, dh_create_cf any occupation */
 #define DH_ORBITAL_FULL 0
 #define DH_ORBITAL_SPARSE 1 /* blocks.py:52-62: 8 features per (j, k) mixed into the M harmonics by
                                lll_weight; folded into the full layout when parameters are set */
@@ -84,6 +86,12 @@ typedef struct dh_config {
 typedef struct dh_handle dh_handle;
 
 int dh_create(const dh_config* cfg, dh_handle** out);
+/* Jain state (cfg->network_type = DH_NETWORK_JAIN) with an explicit occupation: occ holds
+ * [n_occ][2] ints (Lambda level n in {0, 1}, 2 m), one determinant column each in this order;
+ * Q1 = flux/2 - cf_flux (N - 1) >= 0, n_occ = N, 2 m of the parity of 2 Q1, |m| <= Q1 + n,
+ * no orbital twice.  The handle has no parameters and serves dh_logpsi, dh_mcmc_step,
+ * dh_local_energy, dh_potential and dh_energy_stats as a Laughlin handle does. */
+int dh_create_cf(const dh_config* cfg, const int* occ, int n_occ, dh_handle** out);
 void dh_destroy(dh_handle* h);
 const char* dh_last_error(void);
 const char* dh_version(void);

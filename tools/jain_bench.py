@@ -1,0 +1,63 @@
+"""Jain two-Lambda-level state: the native kernels (cf.hip) against the callable route
+(`JainCallable` through deephall_amd.generic: torch.func derivatives of the slogdet form).
+ms per dh_local_energy batch and per dh_logpsi batch at B = 4096; the callable route runs at
+a batch it can afford and is scaled per walker.  Prints one line per N, then the value
+kernel's LDS per walker (what bounds the walkers that share a CU)."""
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, ".")
+sys.path.insert(0, "tests")
+from deephall_amd import config, hamiltonian, make_network  # noqa: E402
+from deephall_amd.networks import JainCallable  # noqa: E402
+from helpers import make_walkers  # noqa: E402
+
+B = 4096
+
+
+def timed(fn, reps=None, window=0.5):
+    """Seconds per call after a warm-up; reps None: as many as fill `window` seconds."""
+    fn()
+    torch.cuda.synchronize()
+    if reps is None:
+        t = time.perf_counter()
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        reps = max(10, int(window / ((time.perf_counter() - t) / 5)))
+    t = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) / reps
+
+
+def value_lds_bytes(N):
+    """cf.hip's value-only layout: u, v per electron, E [N][N], N + 4 pivot entries, complex double."""
+    return 16 * (2 * N + N * N + N + 4)
+
+
+for N, Bc in ((6, 4096), (10, 2048), (12, 1024)):
+    flux = (5 * N - 8) // 2  # N = 4 Q1 + 4, Q1 = Q - (N - 1)
+    system = config.System(nspins=(N, 0), flux=flux)
+    net = config.Network()
+    net.type = config.NetworkType.jain
+    model = make_network(system, net)
+    x = torch.tensor(make_walkers(B, N, seed=5, margin=0.05), device="cuda")
+    p = model.init(0, device="cuda")
+    el = hamiltonian.local_energy(model, system)
+    t_el = timed(lambda: el(p, x))
+    t_lp = timed(lambda: model.apply(p, x))
+    ref = JainCallable((N, 0), flux, system=system)
+    xc = x[:Bc].contiguous()
+    elc = hamiltonian.local_energy(ref, system)
+    c_el = timed(lambda: elc({}, xc), 2) * B / Bc
+    c_lp = timed(lambda: ref(None, xc), 5) * B / Bc
+    print(f"jain N={N:2d} 2Q={flux} B={B}: local energy native {t_el * 1e3:8.3f} ms ({B / t_el:,.0f} E_L/s), "
+          f"callable {c_el * 1e3:9.1f} ms (measured at B={Bc}), ratio {c_el / t_el:6.1f}x;  "
+          f"log psi native {t_lp * 1e3:7.3f} ms, callable {c_lp * 1e3:8.2f} ms, ratio {c_lp / t_lp:6.1f}x", flush=True)
+for N in (6, 10, 12):
+    lds = value_lds_bytes(N)
+    print(f"value kernel N={N:2d}: {lds} B of LDS per walker: LDS alone would let {160 * 1024 // lds} walkers share a CU")
