@@ -43,6 +43,7 @@ class NetworkType(str, enum.Enum):
     psiformer = "psiformer"
     laughlin = "laughlin"
     jain = "jain"
+    pfaffian = "pfaffian"
 
 
 class OrbitalType(str, enum.Enum):
@@ -86,11 +87,20 @@ class JainNetwork:
 
 
 @dataclass
+class PfaffianNetwork:
+    """Moore-Read Pfaffian state (not in the reference; networks/pfaffian.py).  ``cf_flux``: p,
+    2p vortices per electron; the system's flux must be 2p (N - 1) - 1 with N even."""
+
+    cf_flux: int = 1
+
+
+@dataclass
 class Network:
     type: NetworkType = NetworkType.psiformer
     orbital: OrbitalType = OrbitalType.full
     psiformer: PsiformerNetwork = field(default_factory=PsiformerNetwork)
     jain: JainNetwork = field(default_factory=JainNetwork)
+    pfaffian: PfaffianNetwork = field(default_factory=PfaffianNetwork)
 
 
 @dataclass

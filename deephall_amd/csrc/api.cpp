@@ -156,6 +156,7 @@ struct dh_handle {
   bool laughlin = false;          // DH_NETWORK_LAUGHLIN: no parameters, laughlin.hip kernels
   bool jain = false;              // DH_NETWORK_JAIN: a laughlin handle whose kernels are cf.hip's
   int cf_dense = 0;               // its number of level-1 (dense) columns
+  bool pfaffian = false;          // DH_NETWORK_PFAFFIAN: a laughlin handle whose kernels are pfaffian.hip's (no table)
   std::vector<int> expo_host;     // Laughlin exponents [2][N] = (Q1 + m_j, Q1 - m_j); Jain: cf.hip's column table
   int* expo = nullptr;            // device copy (uploaded at first use)
   KfacHost* kfac = nullptr;       // KFAC plan (built at first dh_kfac_* call)
@@ -331,6 +332,27 @@ int create_jain(const dh_config* cfg, const int* occ, int n_occ, dh_handle** out
   *out = h;
   return DH_OK;
 }
+
+// Moore-Read Pfaffian (pfaffian.hip): N even at flux 2 p (N - 1) - 1, nothing else to choose
+int create_pfaffian(const dh_config* cfg, dh_handle** out) {
+  const int N = cfg->n_up + cfg->n_dn, p = cfg->cf_flux;
+  if (cfg->n_up < 0 || cfg->n_dn < 0 || N < 2 || N > 32) return fail(DH_EINVAL, "Pfaffian: need 2 <= N <= 32 electrons");
+  if (N % 2) return fail(DH_EINVAL, "Pfaffian: the paired state needs an even number of electrons");
+  if (p < 1) return fail(DH_EINVAL, "Pfaffian: need cf_flux >= 1");
+  if (cfg->flux < 1 || cfg->flux > 126) return fail(DH_EINVAL, "Pfaffian needs 1 <= flux <= 126");
+  if (cfg->flux != 2 * p * (N - 1) - 1)
+    return fail(DH_EINVAL, "Pfaffian: the state lives at flux 2 cf_flux (N - 1) - 1 = " +
+                               std::to_string(2 * p * (N - 1) - 1) + ", got " + std::to_string(cfg->flux));
+  if (cfg->interaction_type != DH_INTERACTION_COULOMB && cfg->interaction_type != DH_INTERACTION_HARMONIC)
+    return fail(DH_EINVAL, "Pfaffian: bad interaction type");
+  if (pfaffian_smem_bytes(N, true) > 160 * 1024)
+    return fail(DH_EINVAL, "Pfaffian: N = " + std::to_string(N) + " needs " + std::to_string(pfaffian_smem_bytes(N, true)) +
+                               " bytes of LDS; the one-workgroup kernel has 160 KiB");
+  dh_handle* h = analytic_handle(cfg, {});
+  h->pfaffian = true;
+  *out = h;
+  return DH_OK;
+}
 }  // namespace
 
 int dh_create_cf(const dh_config* cfg, const int* occ, int n_occ, dh_handle** out) {
@@ -357,6 +379,7 @@ int dh_create(const dh_config* cfg, dh_handle** out) {
     return DH_OK;
   }
   if (cfg->network_type == DH_NETWORK_JAIN) return create_jain(cfg, nullptr, 0, out);
+  if (cfg->network_type == DH_NETWORK_PFAFFIAN) return create_pfaffian(cfg, out);
   if (cfg->network_type != DH_NETWORK_PSIFORMER) return fail(DH_EINVAL, "bad network type");
   const int N = cfg->n_up + cfg->n_dn;
   if (cfg->n_up < 0 || cfg->n_dn < 0 || N < 1 || N > 32) return fail(DH_EINVAL, "need 1 <= N <= 32 electrons");
@@ -941,9 +964,12 @@ int ensure_expo(dh_handle* h) {
 int value_pass(dh_handle* h, const float* x, int nw, const Work& w, float* logpsi, hipStream_t s,
                bool geo_ready = false, const McmcEpi& epi = McmcEpi{}) {
   if (h->laughlin) {
-    if (int rc = ensure_expo(h)) return rc;
+    if (!h->pfaffian)
+      if (int rc = ensure_expo(h)) return rc;
     PROF(PK_DET_VALUE, 0.0, 8.0 * nw * h->d.N);
-    if (h->jain)
+    if (h->pfaffian)
+      launch_pfaffian(h->d, x, h->cfg.cf_flux, logpsi, nullptr, nullptr, nw, s);
+    else if (h->jain)
       launch_cf(h->d, x, h->expo, h->cf_dense, logpsi, nullptr, nullptr, nw, s);
     else
       launch_laughlin(h->d, x, h->expo, logpsi, nullptr, nullptr, nw, s);
@@ -1042,10 +1068,13 @@ int dh_local_energy(dh_handle* h, const float* x, int B, float* e_l, float* obs,
   if (!e_l || !obs) return fail(DH_EINVAL, "null output");
   const Dims& d = h->d;
   if (h->laughlin) {
-    if (int rc = ensure_expo(h)) return rc;
+    if (!h->pfaffian)
+      if (int rc = ensure_expo(h)) return rc;
     hipStream_t s = (hipStream_t)stream;
     PROF(PK_DET_ENERGY, 0.0, 48.0 * B);
-    if (h->jain)
+    if (h->pfaffian)
+      launch_pfaffian(d, x, h->cfg.cf_flux, nullptr, e_l, obs, B, s);
+    else if (h->jain)
       launch_cf(d, x, h->expo, h->cf_dense, nullptr, e_l, obs, B, s);
     else
       launch_laughlin(d, x, h->expo, nullptr, e_l, obs, B, s);

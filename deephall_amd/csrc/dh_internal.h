@@ -395,6 +395,12 @@ size_t cf_smem_bytes(int N, int n_dense, bool energy);
 void launch_cf(const Dims& d, const float* x, const int* tab, int n_dense, float* logpsi, float* e_l, float* obs,
                int nw, hipStream_t s);
 
+// pfaffian.hip: the same two launches for the Moore-Read Pfaffian state with 2 p vortices per
+// electron (N even, flux 2 p (N - 1) - 1; no table).  LDS per walker by instantiation.
+size_t pfaffian_smem_bytes(int N, bool energy);
+void launch_pfaffian(const Dims& d, const float* x, int p, float* logpsi, float* e_l, float* obs, int nw,
+                     hipStream_t s);
+
 // det.hip: backward of log psi = J + log sum_k det Phi_k for per-walker cotangents ct[nw][2]:
 // dF [nw*N][ld_orb] (all columns written) and jg[nw][2] = ct.re * dJ / d(ee_par, ee_anti)
 void launch_det_bwd(const Dims& d, const float* F, const float* x, const float* jastrow, const float* norm,

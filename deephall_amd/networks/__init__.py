@@ -5,6 +5,7 @@ from __future__ import annotations
 from ..config import Network, NetworkType, System
 from .jain import Jain, JainCallable
 from .laughlin import Laughlin, LaughlinQuasiparticle
+from .pfaffian import MooreRead, MooreReadCallable
 from .psiformer import Psiformer
 
 
@@ -17,6 +18,8 @@ def make_network(system: System, network: Network) -> Psiformer:
     if ntype == NetworkType.jain.value:  # cf.hip; occupation None: both Lambda levels filled
         return Jain(flux=system.flux, nspins=system.nspins, cf_flux=network.jain.cf_flux,
                     occupation=network.jain.occupation, system=system)
+    if ntype == NetworkType.pfaffian.value:  # pfaffian.hip: Moore-Read at flux 2p(N-1)-1
+        return MooreRead(flux=system.flux, nspins=system.nspins, cf_flux=network.pfaffian.cf_flux, system=system)
     if ntype == NetworkType.psiformer.value:
         return Psiformer(
             Q=Q,
@@ -31,4 +34,5 @@ def make_network(system: System, network: Network) -> Psiformer:
     raise ValueError(f"unknown network type {network.type}")
 
 
-__all__ = ["make_network", "Psiformer", "Laughlin", "LaughlinQuasiparticle", "Jain", "JainCallable"]
+__all__ = ["make_network", "Psiformer", "Laughlin", "LaughlinQuasiparticle", "Jain", "JainCallable",
+           "MooreRead", "MooreReadCallable"]

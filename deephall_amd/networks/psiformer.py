@@ -82,7 +82,7 @@ class NetworkSpec:
         c.num_heads, c.heads_dim, c.num_layers = self.num_heads, self.heads_dim, self.num_layers
         c.ndets = self.ndets
         c.orbital_type = {"full": 0, "sparse": 1}.get(str(getattr(self.orbital_type, "value", self.orbital_type)), -1)
-        c.network_type = {"psiformer": 0, "laughlin": 1, "jain": 2}.get(str(getattr(self.network_type, "value", self.network_type)), -1)
+        c.network_type = {"psiformer": 0, "laughlin": 1, "jain": 2, "pfaffian": 3}.get(str(getattr(self.network_type, "value", self.network_type)), -1)
         c.excitation_lz = float(self.excitation_lz)
         c.cf_flux = int(self.cf_flux)
         return c
@@ -193,8 +193,8 @@ def flatten_params(params) -> dict:
 
 def param_shapes(spec: NetworkSpec) -> dict:
     """Shapes of the reference's parameter tree (Flax auto-naming)."""
-    if spec.network_type in ("laughlin", "jain"):
-        return {}  # laughlin.py has no parameters; neither has the Jain state
+    if spec.network_type in ("laughlin", "jain", "pfaffian"):
+        return {}  # laughlin.py has no parameters; neither have the Jain and Moore-Read states
     D, H, dh = spec.D, spec.num_heads, spec.heads_dim
     M, N, K = spec.M, spec.nelec, spec.ndets
     p = "PsiformerLayers_0/"

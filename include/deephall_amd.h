@@ -56,6 +56,8 @@ extern "C" {
 #define DH_NETWORK_LAUGHLIN 1 /* networks/laughlin.py: ground state, quasihole, quasiparticle (no parameters) */
 #define DH_NETWORK_JAIN 2 /* Jain composite-fermion state, two Lambda levels (no parameters): dh_create builds the
                             filled-levels ground state N = 4 Q1 + 4, dh_create_cf any occupation */
+#define DH_NETWORK_PFAFFIAN 3 /* Moore-Read Pfaffian state (no parameters): N even, p = cf_flux >= 1 and
+                                flux = 2 p (N - 1) - 1 exactly (nu = 1/2 at p = 1); N <= 28 by the kernel's LDS */
 #define DH_ORBITAL_FULL 0
 #define DH_ORBITAL_SPARSE 1 /* blocks.py:52-62: 8 features per (j, k) mixed into the M harmonics by
                                lll_weight; folded into the full layout when parameters are set */
