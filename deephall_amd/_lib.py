@@ -91,7 +91,11 @@ EXPORTS = [
     "dh_minsr_matrix",
     "dh_ntk_jvp_workspace_bytes",
     "dh_ntk_jvp",
+    "dh_fidelity_partial",
+    "dh_fidelity_residual",
 ]
+
+DH_NFID = 5  # dh_fidelity_partial: m, S re, S im, S2, n
 
 
 PROF_KINDS = ["gemm", "attention", "layernorm", "input", "det_value", "det_energy", "mcmc",
@@ -238,6 +242,10 @@ def load(path: Path | str | None = None):
     lib.dh_ntk_jvp_workspace_bytes.restype = sz
     lib.dh_ntk_jvp.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]
     lib.dh_ntk_jvp.restype = i32
+    lib.dh_fidelity_partial.argtypes = [vp, vp, i32, vp, vp]
+    lib.dh_fidelity_partial.restype = i32
+    lib.dh_fidelity_residual.argtypes = [vp, vp, i32, vp, vp, vp]
+    lib.dh_fidelity_residual.restype = i32
     lib.dh_grad_cotangent.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.dh_grad_cotangent.restype = i32
     lib.dh_adam_update.argtypes = [vp, vp, vp, vp, sz, f32, f32, f32, f32, i32, vp]

@@ -158,6 +158,23 @@ class OptimizerMinsr:
 
 
 @dataclass
+class Pretrain:
+    """Fidelity pretraining onto a trial state before the energy minimisation (pretrain.py; not
+    in the reference).  ``iterations``: 0 switches it off.  ``reference``: "laughlin", "jain" or
+    "pfaffian", built for the run's system as the overlap estimator builds it (``network.jain`` /
+    ``network.pfaffian`` choose p and the occupation).  ``lr``: None is the chosen optimizer's own
+    schedule; either way it starts at t = 0 and the training after it starts at t = 0 again."""
+
+    iterations: int = 0
+    reference: str = "laughlin"
+    lr: Optional[LearningRate] = None
+
+    def __post_init__(self):
+        if isinstance(self.lr, dict):  # from a config file
+            self.lr = from_dict(LearningRate, self.lr)
+
+
+@dataclass
 class Optim:
     """config.py:160-165.  The default optimizer is KFAC, as in the reference
     (optimizers.py: make_kfac_training_step on the dh_kfac_* kernels)."""
@@ -167,6 +184,7 @@ class Optim:
     adam: OptimizerAdam = field(default_factory=OptimizerAdam)
     kfac: OptimizerKfac = field(default_factory=OptimizerKfac)
     minsr: OptimizerMinsr = field(default_factory=OptimizerMinsr)
+    pretrain: Pretrain = field(default_factory=Pretrain)
 
 
 @dataclass

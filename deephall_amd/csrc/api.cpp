@@ -2015,6 +2015,21 @@ int dh_loss_diff(dh_handle* h, const float* e_l, const float* obs, int B, const 
   return check_launch();
 }
 
+int dh_fidelity_partial(const float* logpsi, const float* logphi, int B, double* part, void* stream) {
+  if (!logpsi || !logphi || !part) return fail(DH_EINVAL, "dh_fidelity_partial: null argument");
+  if (B < 1) return fail(DH_EINVAL, "dh_fidelity_partial needs B >= 1");
+  launch_fidelity_partial(logpsi, logphi, B, part, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_fidelity_residual(const float* logpsi, const float* logphi, int B, const double* total, float* resid,
+                         void* stream) {
+  if (!logpsi || !logphi || !total || !resid) return fail(DH_EINVAL, "dh_fidelity_residual: null argument");
+  if (B < 1) return fail(DH_EINVAL, "dh_fidelity_residual needs B >= 1");
+  launch_fidelity_residual(logpsi, logphi, B, total, resid, (hipStream_t)stream);
+  return check_launch();
+}
+
 // Debug hook (tests only): run input + trunk + orbital GEMM for B walkers with
 // C = 1 (op 0) or 2N+5 (op 1) channels and leave the results in the workspace:
 // final trunk activations at float offset 0 ([rows][D]) and orbital features at

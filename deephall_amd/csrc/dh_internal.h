@@ -494,6 +494,10 @@ void launch_ntk_features(const Dims& d, const float* geo, int rows, float* out, 
 size_t minsr_matrix_ws_doubles(int Bg);
 void launch_minsr_matrix(const float* T, const unsigned char* valid, int Bg, double damping, double* A, double* ws,
                          hipStream_t s);
+// fidelity.hip: dh_fidelity_partial (part [DH_NFID] doubles) and dh_fidelity_residual
+void launch_fidelity_partial(const float* logpsi, const float* logphi, int B, double* part, hipStream_t s);
+void launch_fidelity_residual(const float* logpsi, const float* logphi, int B, const double* total, float* resid,
+                              hipStream_t s);
 
 }  // namespace dh
 

@@ -223,11 +223,11 @@ class LogManager:
         return step, CheckpointState(params, shard, opt_state, width)
 
     @contextmanager
-    def create_writer(self):
+    def create_writer(self, name: str = "train_stats.csv"):
         if not self.rank0:
             yield _NullWriter()
             return
-        with StatsWriter(self.save_path / "train_stats.csv") as writer:
+        with StatsWriter(self.save_path / name) as writer:
             yield writer
 
 

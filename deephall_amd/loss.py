@@ -111,7 +111,7 @@ def _kfac_buffer(net, device):
     return cache[device]
 
 
-def make_loss_fn(network, system, mode: LossMode = LossMode.ENERGY_GRAD, curvature: bool = False):
+def make_loss_fn(network, system, mode: LossMode = LossMode.ENERGY_GRAD, curvature: bool = False, residual=None):
     """loss.py:47-110.  ``loss_and_grad(params, data) -> (LossStats, aux)`` where aux is
     diff [B] complex (ENERGY_DIFF), the real parameter gradient (ENERGY_GRAD, a ParamTree)
     or the complex one ({name: complex tensor}, SR_F_VECTOR).  Every statistic and the
@@ -122,21 +122,34 @@ def make_loss_fn(network, system, mode: LossMode = LossMode.ENERGY_GRAD, curvatu
     the Fisher curvature statistics of the batch — the reference registers
     ``register_normal_predictive_distribution(Re log psi)`` inside this function (loss.py:98)
     for kfac_jax to trace — averaged over ranks in the SAME all-reduce as the gradient and
-    left in ``loss_and_grad.curvature`` (float32 [nstats], dh_kfac_layout)."""
+    left in ``loss_and_grad.curvature`` (float32 [nstats], dh_kfac_layout).
+
+    ``residual`` (pretrain.make_fidelity_residual; not in the reference): a hook
+    ``(params, data) -> (e_l [B, 2], obs [B, 8])`` whose per-walker residual takes the local
+    energy's place in everything that follows — statistics, centring and IQR clip (with no
+    penalties and no handle), cotangents, VJP — and ``stats["fidelity"]`` is its
+    ``last_fidelity``.  None: the energy path, unchanged."""
     pen = (float(system.lz_penalty), float(system.lz_center), float(system.l2_penalty))
     penalties = pen[0] != 0.0 or pen[2] != 0.0
     if native_network(network) is None:
+        if residual is not None:
+            raise TypeError("a residual hook needs a network of this library (Psiformer)")
         return _make_callable_loss_fn(network, system, mode, pen, penalties)
     net = resolve_network(network)
+    if residual is not None:
+        pen, penalties = (0.0, 0.0, 0.0), False
+    snet = net if residual is None else None  # the statistics kernels' (unused) handle
 
     def loss_and_grad(params, data, n_accept=None, steps=1, flags=None):
         """``n_accept`` [B] int (mcmc_step(..., reduce=False).last_n_accept) puts pmove into
         the packed statistics; ``flags`` rides in the same all-reduce (reduce_stats)."""
-        e_l, obs = _run_local_energy(net, params, data)
-        local = device_stats(net, e_l, obs, n_accept, steps, penalties=penalties)
+        e_l, obs = _run_local_energy(net, params, data) if residual is None else residual(params, data)
+        local = device_stats(snet, e_l, obs, n_accept, steps, penalties=penalties)
         stats, g = reduce_stats(local, raw=True, flags=flags)
+        if residual is not None:
+            stats["fidelity"] = residual.last_fidelity
         loss_and_grad.last = (e_l, obs)
-        diff, nvalid = loss_diff(net, e_l, obs, g, *pen)
+        diff, nvalid = loss_diff(snet, e_l, obs, g, *pen)
         if mode == LossMode.ENERGY_DIFF:
             return stats, torch.complex(diff[:, 0], diff[:, 1])
         if curvature:

@@ -71,8 +71,8 @@ def adam_update(params: ParamTree, grads: ParamTree, state: AdamState, lr: float
     state.count += 1
 
 
-def make_adam_training_step(cfg: Config, network):
-    loss_grad_fn = make_loss_fn(network, cfg.system, LossMode.ENERGY_GRAD)
+def make_adam_training_step(cfg: Config, network, residual=None):
+    loss_grad_fn = make_loss_fn(network, cfg.system, LossMode.ENERGY_GRAD, residual=residual)
     net = loss_grad_fn.network
 
     def init(params, key=None, data=None):
@@ -117,11 +117,11 @@ class KfacState:
         self.step = int(d["step"])
 
 
-def make_kfac_training_step(cfg: Config, network):
+def make_kfac_training_step(cfg: Config, network, residual=None):
     """optimizers/kfac.py:195-241: kfac_jax.Optimizer(l2_reg 0, norm_constraint 1e-3,
     curvature_ema 0.95, inverse_update_period 1, estimation_mode fisher_exact, multi_device)
     stepped with momentum 0 and damping 1e-3 at the schedule's learning rate."""
-    loss_grad_fn = make_loss_fn(network, cfg.system, LossMode.ENERGY_GRAD, curvature=True)
+    loss_grad_fn = make_loss_fn(network, cfg.system, LossMode.ENERGY_GRAD, curvature=True, residual=residual)
     net = loss_grad_fn.network
     if str(getattr(cfg.network.orbital, "value", cfg.network.orbital)) == "sparse":
         # kfac.py:127-133, 175-181 (oracle/kfac.py header): the lll_weight block's statistics assume
@@ -342,7 +342,7 @@ def minsr_direction_sharded(net, params: ParamTree, data: torch.Tensor, diff: to
     return delta
 
 
-def make_minsr_training_step(cfg: Config, network):
+def make_minsr_training_step(cfg: Config, network, residual=None):
     """MinSR (Chen & Heyl 2024; Rende et al. 2024): stochastic reconfiguration solved in sample
     space, delta = (S + damping I)^-1 g with S the centred 2B-sample Fisher matrix — exact, where
     KFAC approximates — then KFAC's norm constraint against the ENERGY_GRAD gradient g:
@@ -360,7 +360,7 @@ def make_minsr_training_step(cfg: Config, network):
         raise NotImplementedError("MinSR on more than one rank needs each rank to compute a share of the gathered "
                                   "walkers' Gram matrix: set optim.minsr.sharded (every rank then holds the whole "
                                   "batch's activations and matrices), or run it on a single rank")
-    loss_fn = make_loss_fn(network, cfg.system, LossMode.ENERGY_DIFF)
+    loss_fn = make_loss_fn(network, cfg.system, LossMode.ENERGY_DIFF, residual=residual)
     net = loss_fn.network
     if net is None or not hasattr(net, "ntk"):
         raise TypeError("MinSR needs a Psiformer of this library")
@@ -381,6 +381,7 @@ def make_minsr_training_step(cfg: Config, network):
             delta = minsr_direction_sharded(net, params, data, diff, opt.damping, prev=opt_state.prev, momentum=mu)
         else:
             delta = minsr_direction(net, params, data, diff, opt.damping, prev=opt_state.prev, momentum=mu)
+        step.last_diff, step.last_direction = diff, delta  # what the direction was solved from (tests)
         lr = lr_schedule(opt.lr, opt_state.step)
         d = torch.nan_to_num(delta.flat, nan=0.0, posinf=0.0, neginf=0.0)
         if opt_state.prev is not None:
@@ -409,16 +410,20 @@ def make_inference_step(cfg: Config, network):
     return init, step
 
 
-def make_optimizer_step(cfg: Config, network):
-    """optimizers/__init__.py:25-35."""
+def make_optimizer_step(cfg: Config, network, residual=None):
+    """optimizers/__init__.py:25-35.  ``residual`` (pretrain.make_fidelity_residual): the hook of
+    ``make_loss_fn`` that puts a per-walker residual in the local energy's place; every training
+    step takes it, the inference step has nothing to train (``ValueError``)."""
     name = cfg.optim.optimizer
     name = OptimizerName(getattr(name, "value", name)) if name is not None else OptimizerName.none
     if name == OptimizerName.adam:
-        return make_adam_training_step(cfg, network)
+        return make_adam_training_step(cfg, network, residual=residual)
     if name == OptimizerName.none:
+        if residual is not None:
+            raise ValueError("a residual hook needs an optimizer (adam, kfac or minsr), not 'none'")
         return make_inference_step(cfg, network)
     if name == OptimizerName.kfac:
-        return make_kfac_training_step(cfg, network)
+        return make_kfac_training_step(cfg, network, residual=residual)
     if name == OptimizerName.minsr:
-        return make_minsr_training_step(cfg, network)
+        return make_minsr_training_step(cfg, network, residual=residual)
     raise ValueError(f"Optimizer {name} is not implemented!")

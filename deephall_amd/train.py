@@ -198,7 +198,15 @@ class GracefulKiller:
 
 
 def train(cfg: Config):
-    """train.py:80-167 on MI355X.  Returns the final CheckpointState."""
+    """train.py:80-167 on MI355X.  Returns the final CheckpointState.
+
+    ``optim.pretrain.iterations`` > 0 (not in the reference): a fresh run — step 0, nothing
+    restored — first runs that many fidelity-pretraining iterations towards the trial state
+    (pretrain.py) after burn-in and the initial-energy line, one row each in
+    ``pretrain_stats.csv`` beside ``train_stats.csv``.  The energy minimisation then starts with
+    a new optimizer state and its schedule at t = 0; walkers and MCMC width carry over.
+    Pretraining is not resumable: a checkpoint restore skips it, and a run killed during it
+    starts it over.  With 0 iterations nothing here changes."""
     from . import optimizers
     from .config import OptimizerName
     from .log import LogManager, init_logging
@@ -206,6 +214,11 @@ def train(cfg: Config):
     from .types import CheckpointState
 
     init_logging()
+    npre = int(cfg.optim.pretrain.iterations)
+    if npre > 0:  # a config that cannot pretrain fails before any walker moves
+        from . import pretrain as pre
+
+        pre.make_reference(cfg)
     init_distributed()
     log_manager = LogManager(cfg)
     model = make_network(cfg.system, cfg.network)
@@ -238,6 +251,10 @@ def train(cfg: Config):
             initial_stats, _ = make_loss_fn(model, cfg.system, LossMode.ENERGY_DIFF)(params, data)
             logger.info("Initial energy: %s", float(initial_stats["energy"].real))
     state = CheckpointState(params, data, opt_state, width)
+    if initial_step == 0 and restored is None and npre > 0:
+        with log_manager.create_writer("pretrain_stats.csv") as writer:
+            state, key, _ = pre.pretrain(cfg, model, state, mcmc_step, key, writer=writer)
+        state = state._replace(opt_state=opt_init(state.params, None, state.data))
     last_save_time = time.time()
     killer = GracefulKiller()
     try:

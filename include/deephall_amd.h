@@ -350,6 +350,32 @@ int dh_energy_stats(dh_handle* h, const float* e_l, const float* obs, const int3
 int dh_loss_diff(dh_handle* h, const float* e_l, const float* obs, int B, const float* stats, float lz_penalty,
                  float lz_center, float l2_penalty, float* diff, float* nvalid, void* stream);
 
+/* Fidelity of psi with a trial state phi on walkers drawn from |psi|^2 (pretraining; not in the
+ * reference).  d_b = logphi[b] - logpsi[b] (complex, inputs float32 [B][2] = (Re, Im)); a walker
+ * is valid when its four floats are finite.
+ * dh_fidelity_partial writes part[DH_NFID] doubles (device):
+ *   m = max Re d over the valid walkers (-inf: none), S = sum_b z_b with z_b = e^{d_b - m}
+ *   (re, im), S2 = sum_b |z_b|^2 = sum_b e^{2 (Re d_b - m)}, n = the number of valid walkers.
+ *   Partials of shards combine with M = max m_r, S = sum S_r e^{m_r - M},
+ *   S2 = sum S2_r e^{2 (m_r - M)}, n = sum n_r (shards with n_r = 0 skipped);
+ *   F = |S|^2 / (n S2) estimates |<phi|psi>|^2 / (<phi|phi> <psi|psi>).
+ * dh_fidelity_residual writes resid[B][2] = 1 - n z_b / S (complex division) from such a
+ *   (combined) total: the weights eps_b of d(-log F)/dp = 2 Re mean(conj(d log psi_b / dp) eps_b).
+ *   NaN for an invalid walker; all NaN when n = 0 or S = 0 (|S|^2 = 0 in double).
+ * Double arithmetic from the subtraction on; Im d is folded into [-pi, pi] before sin / cos.
+ * One workgroup reduces in a fixed order, no atomics: two calls give identical bits.  A single
+ * valid walker gives F = 1 and resid = 0 exactly.  Any B >= 1; B < 1 or a null pointer is
+ * DH_EINVAL before any device call. */
+#define DH_NFID 5
+#define DH_FID_M 0     /* max Re d over the valid walkers */
+#define DH_FID_S_RE 1  /* Re sum e^{d - m}                */
+#define DH_FID_S_IM 2  /* Im sum e^{d - m}                */
+#define DH_FID_S2 3    /* sum e^{2 (Re d - m)}            */
+#define DH_FID_N 4     /* number of valid walkers         */
+int dh_fidelity_partial(const float* logpsi, const float* logphi, int B, double* part, void* stream);
+int dh_fidelity_residual(const float* logpsi, const float* logphi, int B, const double* total, float* resid,
+                         void* stream);
+
 /* Potential energy only (make_potential, hamiltonian.py:63-80), NOT multiplied by
  * interaction_strength: pe[B]. */
 int dh_potential(dh_handle* h, const float* x, int B, float* pe, void* stream);
