@@ -153,11 +153,13 @@ struct dh_handle {
   std::vector<float> norm_host;
   bool params_set = false;
   bool ref_set = false;
-  bool laughlin = false;          // DH_NETWORK_LAUGHLIN: no parameters, laughlin.hip kernels
-  bool jain = false;              // DH_NETWORK_JAIN: a laughlin handle whose kernels are cf.hip's
-  int cf_dense = 0;               // its number of level-1 (dense) columns
-  bool pfaffian = false;          // DH_NETWORK_PFAFFIAN: a laughlin handle whose kernels are pfaffian.hip's (no table)
-  std::vector<int> expo_host;     // Laughlin exponents [2][N] = (Q1 + m_j, Q1 - m_j); Jain: cf.hip's column table
+  // Which wavefunction the handle is.  All but the Psiformer are analytic: no parameters, one
+  // kernel file each (laughlin.hip, cf.hip, pfaffian.hip), launched by launch_trial
+  enum State { PSIFORMER, LAUGHLIN, JAIN, PFAFFIAN } state = PSIFORMER;
+  bool analytic() const { return state != PSIFORMER; }
+  int cf_dense = 0;               // Jain: the number of level-1 (dense) columns
+  std::vector<int> expo_host;     // Laughlin exponents [2][N] = (Q1 + m_j, Q1 - m_j); Jain: cf.hip's column table;
+                                  // Pfaffian: empty
   int* expo = nullptr;            // device copy (uploaded at first use)
   KfacHost* kfac = nullptr;       // KFAC plan (built at first dh_kfac_* call)
   Profiler prof;
@@ -196,6 +198,17 @@ const char* dh_last_error(void) { return g_err.c_str(); }
 const char* dh_version(void) { return "deephall_amd 0.1 (gfx950)"; }
 
 namespace {
+// What every analytic state asks of N, the flux and the interaction; name starts the messages
+int check_analytic(const dh_config* cfg, const std::string& name, int n_min) {
+  const int N = cfg->n_up + cfg->n_dn;
+  if (cfg->n_up < 0 || cfg->n_dn < 0 || N < n_min || N > 32)
+    return fail(DH_EINVAL, name + ": need " + std::to_string(n_min) + " <= N <= 32 electrons");
+  if (cfg->flux < 1 || cfg->flux > 126) return fail(DH_EINVAL, name + " needs 1 <= flux <= 126");
+  if (cfg->interaction_type != DH_INTERACTION_COULOMB && cfg->interaction_type != DH_INTERACTION_HARMONIC)
+    return fail(DH_EINVAL, name + ": bad interaction type");
+  return DH_OK;
+}
+
 // Laughlin(nspins, flux, cf_flux, excitation_lz) (laughlin.py:19-46): exponents of the
 // composite-fermion orbitals, in doubled units (2 Q1, 2 m are integers)
 int laughlin_exponents(const dh_config* cfg, std::vector<int>& ex) {
@@ -234,12 +247,12 @@ int laughlin_exponents(const dh_config* cfg, std::vector<int>& ex) {
     return fail(DH_EINVAL, "Laughlin: N too large for the one-workgroup kernel's LDS (160 KiB)");
   return DH_OK;
 }
-// The handle of a parameter-free analytic state (Laughlin, Jain): no network dimensions
-dh_handle* analytic_handle(const dh_config* cfg, const std::vector<int>& ex) {
+// The handle of a parameter-free analytic state: no network dimensions
+dh_handle* analytic_handle(const dh_config* cfg, dh_handle::State state, const std::vector<int>& ex) {
   const int N = cfg->n_up + cfg->n_dn;
   auto* h = new dh_handle();
   h->cfg = *cfg;
-  h->laughlin = true;
+  h->state = state;
   h->expo_host = ex;
   Dims& d = h->d;
   d = Dims{};
@@ -318,16 +331,11 @@ int jain_table(const dh_config* cfg, const int* occ, int n_occ, std::vector<int>
 }
 
 int create_jain(const dh_config* cfg, const int* occ, int n_occ, dh_handle** out) {
-  const int N = cfg->n_up + cfg->n_dn;
-  if (cfg->n_up < 0 || cfg->n_dn < 0 || N < 1 || N > 32) return fail(DH_EINVAL, "Jain: need 1 <= N <= 32 electrons");
-  if (cfg->flux < 1 || cfg->flux > 126) return fail(DH_EINVAL, "Jain needs 1 <= flux <= 126");
-  if (cfg->interaction_type != DH_INTERACTION_COULOMB && cfg->interaction_type != DH_INTERACTION_HARMONIC)
-    return fail(DH_EINVAL, "Jain: bad interaction type");
+  if (int rc = check_analytic(cfg, "Jain", 1)) return rc;
   std::vector<int> tab;
   int n_dense = 0;
   if (int rc = jain_table(cfg, occ, n_occ, tab, n_dense)) return rc;
-  dh_handle* h = analytic_handle(cfg, tab);
-  h->jain = true;
+  dh_handle* h = analytic_handle(cfg, dh_handle::JAIN, tab);
   h->cf_dense = n_dense;
   *out = h;
   return DH_OK;
@@ -336,21 +344,16 @@ int create_jain(const dh_config* cfg, const int* occ, int n_occ, dh_handle** out
 // Moore-Read Pfaffian (pfaffian.hip): N even at flux 2 p (N - 1) - 1, nothing else to choose
 int create_pfaffian(const dh_config* cfg, dh_handle** out) {
   const int N = cfg->n_up + cfg->n_dn, p = cfg->cf_flux;
-  if (cfg->n_up < 0 || cfg->n_dn < 0 || N < 2 || N > 32) return fail(DH_EINVAL, "Pfaffian: need 2 <= N <= 32 electrons");
+  if (int rc = check_analytic(cfg, "Pfaffian", 2)) return rc;
   if (N % 2) return fail(DH_EINVAL, "Pfaffian: the paired state needs an even number of electrons");
   if (p < 1) return fail(DH_EINVAL, "Pfaffian: need cf_flux >= 1");
-  if (cfg->flux < 1 || cfg->flux > 126) return fail(DH_EINVAL, "Pfaffian needs 1 <= flux <= 126");
   if (cfg->flux != 2 * p * (N - 1) - 1)
     return fail(DH_EINVAL, "Pfaffian: the state lives at flux 2 cf_flux (N - 1) - 1 = " +
                                std::to_string(2 * p * (N - 1) - 1) + ", got " + std::to_string(cfg->flux));
-  if (cfg->interaction_type != DH_INTERACTION_COULOMB && cfg->interaction_type != DH_INTERACTION_HARMONIC)
-    return fail(DH_EINVAL, "Pfaffian: bad interaction type");
   if (pfaffian_smem_bytes(N, true) > 160 * 1024)
     return fail(DH_EINVAL, "Pfaffian: N = " + std::to_string(N) + " needs " + std::to_string(pfaffian_smem_bytes(N, true)) +
                                " bytes of LDS; the one-workgroup kernel has 160 KiB");
-  dh_handle* h = analytic_handle(cfg, {});
-  h->pfaffian = true;
-  *out = h;
+  *out = analytic_handle(cfg, dh_handle::PFAFFIAN, {});
   return DH_OK;
 }
 }  // namespace
@@ -368,14 +371,10 @@ int dh_create(const dh_config* cfg, dh_handle** out) {
     return fail(DH_EINVAL, "dh_config.struct_size must equal sizeof(dh_config) (" + std::to_string(sizeof(dh_config)) +
                                " bytes); the caller's binding has a different layout");
   if (cfg->network_type == DH_NETWORK_LAUGHLIN) {
-    const int N = cfg->n_up + cfg->n_dn;
-    if (cfg->n_up < 0 || cfg->n_dn < 0 || N < 1 || N > 32) return fail(DH_EINVAL, "need 1 <= N <= 32 electrons");
-    if (cfg->flux < 1 || cfg->flux > 126) return fail(DH_EINVAL, "Laughlin needs 1 <= flux <= 126");
-    if (cfg->interaction_type != DH_INTERACTION_COULOMB && cfg->interaction_type != DH_INTERACTION_HARMONIC)
-      return fail(DH_EINVAL, "bad interaction type");
+    if (int rc = check_analytic(cfg, "Laughlin", 1)) return rc;
     std::vector<int> ex;
     if (int rc = laughlin_exponents(cfg, ex)) return rc;
-    *out = analytic_handle(cfg, ex);
+    *out = analytic_handle(cfg, dh_handle::LAUGHLIN, ex);
     return DH_OK;
   }
   if (cfg->network_type == DH_NETWORK_JAIN) return create_jain(cfg, nullptr, 0, out);
@@ -740,7 +739,7 @@ void pack_from_ref(dh_handle* h, hipStream_t st) {
 extern "C" {
 
 int dh_set_params(dh_handle* h, const float* params, size_t count, void* stream) {
-  if (h && h->laughlin) return count == 0 ? DH_OK : fail(DH_EINVAL, "the Laughlin wavefunction has no parameters");
+  if (h && h->analytic()) return count == 0 ? DH_OK : fail(DH_EINVAL, "the Laughlin wavefunction has no parameters");
   if (!h || !params) return fail(DH_EINVAL, "null argument");
   if (count != h->offsets.back()) return fail(DH_EINVAL, "parameter count mismatch");
   if (int rc = ensure_param_buffers(h)) return rc;
@@ -760,7 +759,7 @@ int dh_ref_layout(const dh_handle* h, size_t* offsets, int n) {
 }
 
 int dh_set_params_ref(dh_handle* h, const float* ref, size_t count, void* stream) {
-  if (h && h->laughlin) return count == 0 ? DH_OK : fail(DH_EINVAL, "the Laughlin wavefunction has no parameters");
+  if (h && h->analytic()) return count == 0 ? DH_OK : fail(DH_EINVAL, "the Laughlin wavefunction has no parameters");
   if (!h || !ref) return fail(DH_EINVAL, "null argument");
   if (count != h->ref_offsets.back()) return fail(DH_EINVAL, "reference parameter count mismatch");
   if (int rc = ensure_param_buffers(h)) return rc;
@@ -952,29 +951,28 @@ int run_trunk(dh_handle* h, const float* x, int nw, int C, const Work& w, hipStr
   return Trunk{h, h->d, h->p, w, s, nw, C, nw * h->d.N * C, w.route, keep_h}.run(x, geo_ready);
 }
 
-int ensure_expo(dh_handle* h) {
-  if (h->expo) return DH_OK;
-  HIP_TRY(hipMalloc(&h->expo, h->expo_host.size() * sizeof(int)));
-  HIP_TRY(hipMemcpy(h->expo, h->expo_host.data(), h->expo_host.size() * sizeof(int), hipMemcpyHostToDevice));
-  return DH_OK;
+// The kernel of an analytic state on nw walkers: log psi [nw][2] (e_l == nullptr), or the local
+// energy e_l [nw][2] and obs [nw][8].  Uploads the state's table at first use if it has one.
+int launch_trial(dh_handle* h, const float* x, float* logpsi, float* e_l, float* obs, int nw, hipStream_t s) {
+  if (!h->expo && !h->expo_host.empty()) {
+    HIP_TRY(hipMalloc(&h->expo, h->expo_host.size() * sizeof(int)));
+    HIP_TRY(hipMemcpy(h->expo, h->expo_host.data(), h->expo_host.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  PROF(e_l ? PK_DET_ENERGY : PK_DET_VALUE, 0.0, e_l ? 48.0 * nw : 8.0 * nw * h->d.N);
+  if (h->state == dh_handle::PFAFFIAN)
+    launch_pfaffian(h->d, x, h->cfg.cf_flux, logpsi, e_l, obs, nw, s);
+  else if (h->state == dh_handle::JAIN)
+    launch_cf(h->d, x, h->expo, h->cf_dense, logpsi, e_l, obs, nw, s);
+  else
+    launch_laughlin(h->d, x, h->expo, logpsi, e_l, obs, nw, s);
+  return check_launch();
 }
 
-// log psi of nw walkers into logpsi [nw][2]: the Psiformer pass or the Laughlin kernel
+// log psi of nw walkers into logpsi [nw][2]: the Psiformer pass or an analytic state's kernel (launch_trial)
 // epi (Psiformer only): the MCMC accept / next proposal fused into the value kernel
 int value_pass(dh_handle* h, const float* x, int nw, const Work& w, float* logpsi, hipStream_t s,
                bool geo_ready = false, const McmcEpi& epi = McmcEpi{}) {
-  if (h->laughlin) {
-    if (!h->pfaffian)
-      if (int rc = ensure_expo(h)) return rc;
-    PROF(PK_DET_VALUE, 0.0, 8.0 * nw * h->d.N);
-    if (h->pfaffian)
-      launch_pfaffian(h->d, x, h->cfg.cf_flux, logpsi, nullptr, nullptr, nw, s);
-    else if (h->jain)
-      launch_cf(h->d, x, h->expo, h->cf_dense, logpsi, nullptr, nullptr, nw, s);
-    else
-      launch_laughlin(h->d, x, h->expo, logpsi, nullptr, nullptr, nw, s);
-    return check_launch();
-  }
+  if (h->analytic()) return launch_trial(h, x, logpsi, nullptr, nullptr, nw, s);
   if (int rc = run_trunk(h, x, nw, 1, w, s, geo_ready)) return rc;
   {
     PROF(PK_DET_VALUE, 0.0, 4.0 * nw * h->d.N * h->d.ld_orb);
@@ -1019,10 +1017,10 @@ int dh_mcmc_step(dh_handle* h, float* x, float* lp, int32_t* n_accept, int B, in
   const size_t nstride = (size_t)B * (2 * d.N + 1);
   // step st: accept of st - 1 and the proposal of st in one launch (which also writes the
   // proposal's geometry, so the trunk skips its input kernel); the last accept alone
-  const bool geo = !h->laughlin;
+  const bool geo = !h->analytic();
   // Psiformer: step st's accept and step st + 1's proposal run in the epilogue of step st's
   // value kernel (McmcEpi, det.hip): one launch fewer per move, bit-identical results; the
-  // Laughlin kernel keeps the separate accept / proposal launches
+  // analytic states' kernels (launch_trial) keep the separate accept / proposal launches
   const bool fuse = geo;
   for (int st = 0; st < steps; ++st) {
     const float* nz = noise ? noise + st * nstride : nullptr;
@@ -1067,19 +1065,7 @@ int dh_local_energy(dh_handle* h, const float* x, int B, float* e_l, float* obs,
   if (int rc = check_common(h, x, B, ws, ws_bytes, need1)) return rc;
   if (!e_l || !obs) return fail(DH_EINVAL, "null output");
   const Dims& d = h->d;
-  if (h->laughlin) {
-    if (!h->pfaffian)
-      if (int rc = ensure_expo(h)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    PROF(PK_DET_ENERGY, 0.0, 48.0 * B);
-    if (h->pfaffian)
-      launch_pfaffian(d, x, h->cfg.cf_flux, nullptr, e_l, obs, B, s);
-    else if (h->jain)
-      launch_cf(d, x, h->expo, h->cf_dense, nullptr, e_l, obs, B, s);
-    else
-      launch_laughlin(d, x, h->expo, nullptr, e_l, obs, B, s);
-    return check_launch();
-  }
+  if (h->analytic()) return launch_trial(h, x, nullptr, e_l, obs, B, (hipStream_t)stream);
   // largest chunk that fits the workspace
   int chunk = B;
   while (chunk > 1 && dh_workspace_bytes(h, chunk, 1) > ws_bytes) chunk = (chunk + 1) / 2;
@@ -1751,7 +1737,7 @@ int dh_logpsi_vjp(dh_handle* h, const float* x, int B, const float* ct, float* g
                   size_t ws_bytes, void* stream) {
   const size_t need1 = h ? dh_vjp_workspace_bytes(h, 1) : 0;
   if (int rc = check_common(h, x, B, ws, ws_bytes, need1)) return rc;
-  if (h && h->laughlin) return fail(DH_EINVAL, "the Laughlin wavefunction has no parameters to differentiate");
+  if (h && h->analytic()) return fail(DH_EINVAL, "the Laughlin wavefunction has no parameters to differentiate");
   if (!h->ref_set) return fail(DH_ESTATE, "the VJP needs parameters uploaded with dh_set_params_ref");
   if (!ct || !grad) return fail(DH_EINVAL, "null argument");
   if (h->d.D > 1024 || h->d.dh > 1024) return fail(DH_EINVAL, "VJP supports D <= 1024");
@@ -1769,12 +1755,12 @@ int dh_logpsi_vjp(dh_handle* h, const float* x, int B, const float* ct, float* g
 }
 
 size_t dh_ntk_workspace_bytes(const dh_handle* h, int batch) {
-  if (!h || h->laughlin || h->d.sparse || batch < 1) return 0;
+  if (!h || h->analytic() || h->d.sparse || batch < 1) return 0;
   return carve_ntk(h->d, batch, nullptr).total_bytes;
 }
 
 int dh_ntk_tile_walkers(const dh_handle* h) {
-  if (!h || h->laughlin || h->d.sparse) return 0;
+  if (!h || h->analytic() || h->d.sparse) return 0;
   return ntk_tile_walkers(h->d.N);
 }
 
@@ -1782,7 +1768,7 @@ int dh_ntk_tile_walkers(const dh_handle* h) {
 static int ntk_check(dh_handle* h, const float* x, int B, const float* ct, float* T, void* ws, size_t ws_bytes,
                      int part, int nparts) {
   if (!h) return fail(DH_EINVAL, "null handle");
-  if (h->laughlin) return fail(DH_EINVAL, "the Laughlin wavefunction has no parameters to differentiate");
+  if (h->analytic()) return fail(DH_EINVAL, "the Laughlin wavefunction has no parameters to differentiate");
   if (h->d.sparse) return fail(DH_EINVAL, "dh_ntk supports orbital type \"full\" only");
   if (!x || B < 1) return fail(DH_EINVAL, "bad walkers");
   if (!ct || !T) return fail(DH_EINVAL, "null argument");
@@ -1825,7 +1811,7 @@ int dh_ntk_part(dh_handle* h, const float* x, int B, const float* ct, float* T, 
 }
 
 size_t dh_ntk_jvp_workspace_bytes(const dh_handle* h, int batch) {
-  if (!h || h->laughlin || h->d.sparse || batch < 1) return 0;
+  if (!h || h->analytic() || h->d.sparse || batch < 1) return 0;
   return carve_ntk(h->d, batch, nullptr, /*jvp=*/true).total_bytes;
 }
 
@@ -1833,7 +1819,7 @@ int dh_ntk_jvp(dh_handle* h, const float* x, int B, const float* ct, const float
                float* logpsi, void* ws, size_t ws_bytes, int part, int nparts, void* stream) {
   // dh_ntk_part's checks (T may be null), then this call's own: all before the first device call
   if (!h) return fail(DH_EINVAL, "null handle");
-  if (h->laughlin) return fail(DH_EINVAL, "the Laughlin wavefunction has no parameters to differentiate");
+  if (h->analytic()) return fail(DH_EINVAL, "the Laughlin wavefunction has no parameters to differentiate");
   if (h->d.sparse) return fail(DH_EINVAL, "dh_ntk_jvp supports orbital type \"full\" only");
   if (!x || B < 1) return fail(DH_EINVAL, "bad walkers");
   if (!ct || !v || !jv) return fail(DH_EINVAL, "null argument");
@@ -1884,7 +1870,7 @@ int dh_minsr_matrix(const float* T, const unsigned char* valid, int Bg, double d
 }
 
 int dh_kfac_layout(dh_handle* h, size_t* out, int n) {
-  if (!h || h->laughlin) return fail(DH_EINVAL, "KFAC needs a Psiformer handle");
+  if (!h || h->analytic()) return fail(DH_EINVAL, "KFAC needs a Psiformer handle");
   if (int rc = kfac_plan(h)) return rc;
   const KfacHost& K = *h->kfac;
   // [0] statistics floats, [1] factor-matrix floats, [2] slots, [3] dense blocks, [4] generic
@@ -1908,7 +1894,7 @@ size_t dh_kfac_workspace_bytes(const dh_handle* h, int batch) {
 
 int dh_kfac_vjp(dh_handle* h, const float* x, int B, const float* ct, float* grad, float* stats, float* logpsi,
                 void* ws, size_t ws_bytes, void* stream) {
-  if (!h || h->laughlin) return fail(DH_EINVAL, "KFAC needs a Psiformer handle");
+  if (!h || h->analytic()) return fail(DH_EINVAL, "KFAC needs a Psiformer handle");
   const size_t nref = h->ref_offsets.back();
   const size_t need1 = dh_kfac_workspace_bytes(h, 1);
   if (int rc = check_common(h, x, B, ws, ws_bytes, need1)) return rc;
@@ -1966,7 +1952,7 @@ int dh_kfac_vjp(dh_handle* h, const float* x, int B, const float* ct, float* gra
 int dh_kfac_step(dh_handle* h, float* raw, const float* stats, float ema, float weight, const float* grad,
                  float* params, float lr, float damping, float norm_constraint, float* pgrad, double* info, void* ws,
                  size_t ws_bytes, void* stream) {
-  if (!h || h->laughlin) return fail(DH_EINVAL, "KFAC needs a Psiformer handle");
+  if (!h || h->analytic()) return fail(DH_EINVAL, "KFAC needs a Psiformer handle");
   if (!raw || !grad || !pgrad || !info || !ws) return fail(DH_EINVAL, "null argument");
   if (!(weight > 0.f) || !(damping > 0.f)) return fail(DH_EINVAL, "KFAC needs weight > 0 and damping > 0");
   if (int rc = kfac_device(h)) return rc;
@@ -2079,7 +2065,7 @@ int dh_debug_gemm(int variant, const float* X, int ldx, const float* W, int ldw,
 int dh_debug_gemm_x6_choice(int rows, int ncols) { return gemm_x6_choose(rows, ncols); }
 
 int dh_debug_route(const dh_handle* h, int B, int op, int* out, int n) {
-  if (!h || h->laughlin || B < 1 || (n > 0 && !out)) return fail(DH_EINVAL, "bad route query");
+  if (!h || h->analytic() || B < 1 || (n > 0 && !out)) return fail(DH_EINVAL, "bad route query");
   const int C = op == 1 ? h->d.C : 1;
   const TrunkRoute r = trunk_route(h->d, h->gemm_mode, C, B * h->d.N * C);
   if (n > 0) std::memcpy(out, &r, sizeof(int) * std::min(n, kTrunkRouteFields));

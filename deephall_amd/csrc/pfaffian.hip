@@ -24,23 +24,10 @@
 // plus the pair part with weight 2 p as in cf.hip.  The full complex Hessian of log psi goes to
 // the kinetic / angular-momentum formulas of hamiltonian.py:115-169 exactly as in laughlin.hip
 // and cf.hip.  One 64-thread workgroup per walker, complex double in LDS.
-#include "dh_internal.h"
-#include "device_common.h"
+#include "trial_common.h"
 
 namespace dh {
 namespace {
-
-struct zd {
-  double re, im;
-};
-__device__ __forceinline__ zd operator+(zd a, zd b) { return zd{a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ zd operator-(zd a, zd b) { return zd{a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ zd operator*(zd a, zd b) { return zd{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-__device__ __forceinline__ zd operator*(double s, zd a) { return zd{s * a.re, s * a.im}; }
-__device__ __forceinline__ zd zinv(zd b) {
-  const double d = b.re * b.re + b.im * b.im;
-  return zd{b.re / d, -b.im / d};
-}
 
 // LDS layout in zd units.  Value only: u, v per electron, A [N][N], the two factor columns.
 struct PSm {
@@ -69,30 +56,6 @@ __host__ __device__ inline PSm psm_layout(int N, bool energy) {
   }
   L.total = o;
   return L;
-}
-
-// u, v and their derivatives of electron (th, ph); the first two entries alone if !FULL
-template <bool FULL>
-__device__ void uv_derivs(double th, double ph, zd* q) {
-  double sh, ch, sp, cp;
-  sincos(0.5 * th, &sh, &ch);
-  sincos(0.5 * ph, &sp, &cp);
-  const zd eu{cp, sp}, ev{cp, -sp};  // e^(i phi/2), e^(-i phi/2)
-  const zd u = ch * eu, v = sh * ev;
-  q[0] = u;
-  q[1] = v;
-  if (!FULL) return;
-  const zd I{0.0, 1.0};
-  q[2] = -0.5 * sh * eu;      // du/dth
-  q[3] = 0.5 * (I * u);       // du/dph
-  q[4] = 0.5 * ch * ev;       // dv/dth
-  q[5] = -0.5 * (I * v);      // dv/dph
-  q[6] = -0.25 * u;           // d2u/dth2
-  q[7] = 0.5 * (I * q[2]);    // d2u/dth dph
-  q[8] = -0.25 * u;           // d2u/dph2
-  q[9] = -0.25 * v;           // d2v/dth2
-  q[10] = -0.5 * (I * q[4]);  // d2v/dth dph
-  q[11] = -0.25 * v;          // d2v/dph2
 }
 
 template <bool ENERGY>
@@ -182,22 +145,11 @@ __global__ __launch_bounds__(64) void pfaffian_kernel(const float* __restrict__ 
     __syncthreads();
   }
   // pair part of log psi (value): 2 p sum_{i<j} log w_ij
-  double lre = 0.0, lim = 0.0;
-  for (int q = tid; q < NN; q += nt) {
-    const int i = q / N, j = q % N;
-    if (j <= i) continue;
-    const zd w = UV[SU * i] * UV[SU * j + 1] - UV[SU * j] * UV[SU * i + 1];
-    lre += 0.5 * p2 * log(w.re * w.re + w.im * w.im);
-    lim += p2 * atan2(w.im, w.re);
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    lre += __shfl_xor(lre, o, 64);
-    lim += __shfl_xor(lim, o, 64);
-  }
+  const zd lpair = pair_logpsi(UV, SU, N, p2, false, tid, nt);
   if (!ENERGY) {
     if (tid == 0) {
-      out_lp[2 * b] = (float)(logpf->re + lre);
-      out_lp[2 * b + 1] = (float)remainder(logpf->im + lim, 2.0 * M_PI);
+      out_lp[2 * b] = (float)(logpf->re + lpair.re);
+      out_lp[2 * b + 1] = (float)remainder(logpf->im + lpair.im, 2.0 * M_PI);
     }
     return;
   }
@@ -266,86 +218,7 @@ __global__ __launch_bounds__(64) void pfaffian_kernel(const float* __restrict__ 
     H[idx] = h;
   }
   __syncthreads();
-  // hamiltonian.py:115-169 with g and the full Hessian; potential (double geometry)
-  double v[4] = {0.0, 0.0, 0.0, 0.0};  // KE re, KE im, L2 re, PE
-  double lz = 0.0, lz2 = 0.0;
-  // per electron terms (one thread per electron i), pair terms over (i, j)
-  for (int idx = tid; idx < NN; idx += nt) {
-    const int i = idx / N, j = idx % N;
-    double sti, cti, spi, cpi, stj, ctj, spj, cpj;
-    sincos((double)x[2 * (b * N + i)], &sti, &cti);
-    sincos((double)x[2 * (b * N + i) + 1], &spi, &cpi);
-    sincos((double)x[2 * (b * N + j)], &stj, &ctj);
-    sincos((double)x[2 * (b * N + j) + 1], &spj, &cpj);
-    const zd gti = g[2 * i], gpi = g[2 * i + 1], gtj = g[2 * j], gpj = g[2 * j + 1];
-    const zd htt = H[(2 * i) * T + 2 * j] + gti * gtj, htp = H[(2 * i) * T + 2 * j + 1] + gti * gpj;
-    const zd hpp = H[(2 * i + 1) * T + 2 * j + 1] + gpi * gpj;
-    const double phi_i[3] = {-spi, cpi, 0.0}, phi_j[3] = {-spj, cpj, 0.0};
-    const double thp_i[3] = {cpi * cti / sti, spi * cti / sti, -1.0}, thp_j[3] = {cpj * ctj / stj, spj * ctj / stj, -1.0};
-    const double rj[3] = {stj * cpj, stj * spj, ctj}, ri[3] = {sti * cpi, sti * spi, cti};
-    double pp = 0.0, ptp = 0.0, tt = 0.0, mi_mj = 0.0, mj_phi = 0.0, mj_thp = 0.0;
-    for (int k = 0; k < 3; ++k) {
-      const double mj = Q * (thp_j[k] * ctj + rj[k]), mi = Q * (thp_i[k] * cti + ri[k]);
-      pp += phi_i[k] * phi_j[k];
-      ptp += phi_i[k] * thp_j[k];
-      tt += thp_i[k] * thp_j[k];
-      mi_mj += mi * mj;
-      mj_phi += mj * phi_i[k];
-      mj_thp += mj * thp_i[k];
-    }
-    // 2 phi_i.thp_j P_tp - phi_i.phi_j P_tt - thp_i.thp_j P_pp - 2i m_j.(phi_i g_t_i - thp_i g_p_i) + m_i.m_j
-    zd term = 2.0 * ptp * htp - pp * htt - tt * hpp + zd{mi_mj, 0.0};
-    const zd cross = mj_phi * gti - mj_thp * gpi;
-    term = term - zd{-2.0 * cross.im, 2.0 * cross.re};  // - 2i * cross
-    v[2] += term.re;
-    lz2 -= hpp.re;
-    if (i == j) {
-      const double cot = cti / sti, s2 = sti * sti;
-      // square_grad, grad_grad (Laplacian), magnetic (hamiltonian.py:115-133)
-      const zd sq = gti * gti + (1.0 / s2) * (gpi * gpi);
-      const zd lap = cot * gti + H[(2 * i) * T + 2 * i] + (1.0 / s2) * H[(2 * i + 1) * T + 2 * i + 1];
-      const zd mag = zd{(Q * cot) * (Q * cot), 0.0} + zd{0.0, 2.0 * Q * cti / s2} * gpi;
-      const zd ke = zd{0.0, 0.0} - lap - sq + mag;
-      v[0] += ke.re;
-      v[1] += ke.im;
-      v[2] -= gti.re * cot;  // - sum g_theta cot theta (real part)
-      lz += gpi.im;
-      {
-        double pe = 0.0;
-        for (int jj = i + 1; jj < N; ++jj) {
-          double a1, a2, a3, a4;
-          sincos((double)x[2 * (b * N + jj)], &a1, &a2);
-          sincos((double)x[2 * (b * N + jj) + 1], &a3, &a4);
-          const double u = ri[0] * a1 * a4 + ri[1] * a1 * a3 + ri[2] * a2;
-          pe += interaction == DH_INTERACTION_COULOMB ? 1.0 / sqrt(2.0 - 2.0 * u) : 1.0 + (Q + 1.0) / Q * u;
-        }
-        v[3] += pe;
-      }
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    for (int q = 0; q < 4; ++q) v[q] += __shfl_xor(v[q], o, 64);
-    lz += __shfl_xor(lz, o, 64);
-    lz2 += __shfl_xor(lz2, o, 64);
-  }
-  if (tid == 0) {
-    const double r2 = radius * radius;
-    double pe = v[3];
-    if (interaction == DH_INTERACTION_COULOMB) pe /= radius;
-    pe *= lambda;
-    const double ke_re = v[0] / (2.0 * r2), ke_im = v[1] / (2.0 * r2);
-    e_l[2 * b] = (float)(ke_re + pe);
-    e_l[2 * b + 1] = (float)ke_im;
-    float* ob = obs + 8 * (size_t)b;
-    ob[0] = (float)ke_re;
-    ob[1] = (float)ke_im;
-    ob[2] = (float)pe;
-    ob[3] = (float)lz;
-    ob[4] = (float)lz2;
-    ob[5] = (float)v[2];
-    ob[6] = (float)(logpf->re + lre);
-    ob[7] = (float)remainder(logpf->im + lim, 2.0 * M_PI);
-  }
+  hamiltonian_tail(x, b, N, g, H, Q, radius, lambda, interaction, logpf, lpair, e_l, obs, tid, nt);
 }
 
 }  // namespace

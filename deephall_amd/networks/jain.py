@@ -26,8 +26,7 @@ from __future__ import annotations
 
 import torch
 
-from .laughlin import Laughlin, laughlin_q1
-from .psiformer import NetworkSpec
+from .laughlin import Laughlin, analytic_spec, laughlin_q1
 
 
 def default_occupation(nspins, flux, cf_flux: int = 1) -> tuple:
@@ -77,14 +76,8 @@ class Jain(Laughlin):
         else:
             occ2 = check_occupation(self.nspins, self.flux, self.cf_flux, occupation)
             self.occupation = tuple((n, m2 / 2) for n, m2 in occ2)
-        radius = getattr(system, "radius", None) if system is not None else None
-        lam = getattr(system, "interaction_strength", 1.0) if system is not None else 1.0
-        itype = getattr(system, "interaction_type", "coulomb") if system is not None else "coulomb"
-        self.spec = NetworkSpec(
-            nspins=self.nspins, flux=self.flux, ndets=1, num_heads=1, heads_dim=4, num_layers=0,
-            radius=radius, interaction_strength=float(lam), interaction_type=str(getattr(itype, "value", itype)),
-            network_type="jain", cf_flux=self.cf_flux, occupation=occ2,
-        )
+        self.spec = analytic_spec(system, nspins=self.nspins, flux=self.flux, network_type="jain",
+                                  cf_flux=self.cf_flux, occupation=occ2)
         self._flat_cache = {}
         self._epoch = 0
 

@@ -24,6 +24,19 @@ from .. import _lib
 from .psiformer import NetworkSpec, ParamTree, Psiformer, _ptr, _stream, get_handle
 
 
+def analytic_spec(system, **fields) -> NetworkSpec:
+    """The NetworkSpec of a parameter-free trial state (Laughlin, Jain, MooreRead): no network
+    dimensions, the sphere and the interaction from ``system``, the state's own fields as keywords."""
+    radius = getattr(system, "radius", None) if system is not None else None
+    lam = getattr(system, "interaction_strength", 1.0) if system is not None else 1.0
+    itype = getattr(system, "interaction_type", "coulomb") if system is not None else "coulomb"
+    return NetworkSpec(
+        ndets=1, num_heads=1, heads_dim=4, num_layers=0,
+        radius=radius, interaction_strength=float(lam), interaction_type=str(getattr(itype, "value", itype)),
+        **fields,
+    )
+
+
 class Laughlin(Psiformer):
     """Parameter-free analytic wavefunction sharing the Psiformer's native plumbing."""
 
@@ -33,14 +46,8 @@ class Laughlin(Psiformer):
         self.cf_flux = int(cf_flux)
         self.excitation_lz = float(excitation_lz)
         self.Q = self.flux / 2
-        radius = getattr(system, "radius", None) if system is not None else None
-        lam = getattr(system, "interaction_strength", 1.0) if system is not None else 1.0
-        itype = getattr(system, "interaction_type", "coulomb") if system is not None else "coulomb"
-        self.spec = NetworkSpec(
-            nspins=self.nspins, flux=self.flux, ndets=1, num_heads=1, heads_dim=4, num_layers=0,
-            radius=radius, interaction_strength=float(lam), interaction_type=str(getattr(itype, "value", itype)),
-            network_type="laughlin", excitation_lz=self.excitation_lz, cf_flux=self.cf_flux,
-        )
+        self.spec = analytic_spec(system, nspins=self.nspins, flux=self.flux, network_type="laughlin",
+                                  excitation_lz=self.excitation_lz, cf_flux=self.cf_flux)
         self._flat_cache = {}
         self._epoch = 0
 

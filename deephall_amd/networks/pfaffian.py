@@ -23,8 +23,7 @@ import math
 
 import torch
 
-from .laughlin import Laughlin
-from .psiformer import NetworkSpec
+from .laughlin import Laughlin, analytic_spec
 
 
 def check_pfaffian(nspins, flux, cf_flux: int = 1) -> int:
@@ -49,14 +48,8 @@ class MooreRead(Laughlin):
         self.cf_flux = int(cf_flux)
         self.Q = self.flux / 2
         check_pfaffian(self.nspins, self.flux, self.cf_flux)
-        radius = getattr(system, "radius", None) if system is not None else None
-        lam = getattr(system, "interaction_strength", 1.0) if system is not None else 1.0
-        itype = getattr(system, "interaction_type", "coulomb") if system is not None else "coulomb"
-        self.spec = NetworkSpec(
-            nspins=self.nspins, flux=self.flux, ndets=1, num_heads=1, heads_dim=4, num_layers=0,
-            radius=radius, interaction_strength=float(lam), interaction_type=str(getattr(itype, "value", itype)),
-            network_type="pfaffian", cf_flux=self.cf_flux,
-        )
+        self.spec = analytic_spec(system, nspins=self.nspins, flux=self.flux, network_type="pfaffian",
+                                  cf_flux=self.cf_flux)
         self._flat_cache = {}
         self._epoch = 0
 
