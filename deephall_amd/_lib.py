@@ -67,6 +67,8 @@ EXPORTS = [
     "dh_debug_gemm_x6",
     "dh_debug_gemm_x6_choice",
     "dh_debug_route",
+    "dh_debug_set_det_in_chain",
+    "dh_debug_det_in_chain",
     "dh_ref_layout",
     "dh_set_params_ref",
     "dh_vjp_workspace_bytes",
@@ -206,6 +208,10 @@ def load(path: Path | str | None = None):
     lib.dh_debug_gemm_x6_choice.restype = i32
     lib.dh_debug_route.argtypes = [vp, i32, i32, C.POINTER(i32), i32]
     lib.dh_debug_route.restype = i32
+    lib.dh_debug_set_det_in_chain.argtypes = [i32]
+    lib.dh_debug_set_det_in_chain.restype = i32
+    lib.dh_debug_det_in_chain.argtypes = [vp, i32, i32]
+    lib.dh_debug_det_in_chain.restype = i32
     lib.dh_ref_layout.argtypes = [vp, C.POINTER(sz), i32]
     lib.dh_ref_layout.restype = i32
     lib.dh_set_params_ref.argtypes = [vp, vp, sz, vp]

@@ -815,6 +815,10 @@ struct Trunk {
   const int nw, C, rows;
   const TrunkRoute r;
   const bool keep_h;
+  // the value kernel's work as the tail of the last layer's chain launch (route.det_in_chain;
+  // null: F to HBM for a launch of its own); keep_F: the tail's launch writes F to HBM as well
+  const ChainDet* det = nullptr;
+  const bool keep_F = false;
   const int D = d.D, KO = ofeat_k(d);  // KO: layer 1's o~ row length
   const int ch = C > 1 ? PK_CH : 0;    // profiler class offset of channel-row launches
   const double R = rows, DD = D, f4 = 4.0;
@@ -845,7 +849,8 @@ struct Trunk {
     launch_chain_x6(w.o, attn ? P.UP : lp.WolP, x6_plane_rows(D), lp.bol, lp.ln1, lp.WmP, x6_plane_rows(D), lp.bm,
                     lp.ln2, last ? P.WorbP : P.layer[l + 1].WqkvP, x6_plane_rows(n3),
                     last ? P.borb : P.layer[l + 1].bqkv, n3, last ? w.F : w.qkv, last ? d.ld_orb : 3 * D, w.h, rows,
-                    feat, s, /*store_h=*/!last || keep_h);  // the last layer's h is dead: only its orbitals are read
+                    feat, s, /*store_h=*/!last || keep_h,  // the last layer's h is dead: only its orbitals are read
+                    last ? det : nullptr, /*store_F=*/!(last && det) || keep_F);
   }
   // log psi: each GEMM carries its LayerNorm in the epilogue, in place over h
   void layer_ln_epilogue(int l) const {
@@ -947,8 +952,27 @@ struct Trunk {
 // The pass w was carved for: leaves the orbital features in w.F (where the route maps them) and,
 // with keep_h, the trunk's h in w.h (the chain form skips the last layer's otherwise).
 int run_trunk(dh_handle* h, const float* x, int nw, int C, const Work& w, hipStream_t s, bool geo_ready = false,
-              bool keep_h = false) {
-  return Trunk{h, h->d, h->p, w, s, nw, C, nw * h->d.N * C, w.route, keep_h}.run(x, geo_ready);
+              bool keep_h = false, const ChainDet* det = nullptr, bool keep_F = false) {
+  return Trunk{h, h->d, h->p, w, s, nw, C, nw * h->d.N * C, w.route, keep_h, det, keep_F}.run(x, geo_ready);
+}
+
+// launch_det_value's arguments for a pass whose route carries the determinant tail
+ChainDet chain_det(const dh_handle* h, const float* x, int nw, float* logpsi, const McmcEpi& epi) {
+  const Dims& d = h->d;
+  ChainDet c;
+  c.x = x;
+  c.jastrow = h->p.jastrow;
+  c.norm = h->norm;
+  c.logpsi = logpsi;
+  c.N = d.N;
+  c.n_up = d.n_up;
+  c.M = d.M;
+  c.K = d.K;
+  c.nw = nw;
+  c.per = det_value_per(d);
+  c.ldf = det_chain_ldf(d);
+  c.epi = epi;
+  return c;
 }
 
 // The kernel of an analytic state on nw walkers: log psi [nw][2] (e_l == nullptr), or the local
@@ -973,6 +997,14 @@ int launch_trial(dh_handle* h, const float* x, float* logpsi, float* e_l, float*
 int value_pass(dh_handle* h, const float* x, int nw, const Work& w, float* logpsi, hipStream_t s,
                bool geo_ready = false, const McmcEpi& epi = McmcEpi{}) {
   if (h->analytic()) return launch_trial(h, x, logpsi, nullptr, nullptr, nw, s);
+  // envelope, Jastrow, determinant, accept and proposal in the last chain launch.  Not while the
+  // profiler records (dh_profile_enable): it times kernel classes by events around launches, and
+  // the determinant class inside a GEMM-class launch cannot be timed (nor that launch's FLOP
+  // rate read), so a profiled pass launches the value kernel on its own: the same bits
+  if (w.route.det_in_chain && !h->prof.on) {
+    const ChainDet det = chain_det(h, x, nw, logpsi, epi);
+    return run_trunk(h, x, nw, 1, w, s, geo_ready, false, &det);
+  }
   if (int rc = run_trunk(h, x, nw, 1, w, s, geo_ready)) return rc;
   {
     PROF(PK_DET_VALUE, 0.0, 4.0 * nw * h->d.N * h->d.ld_orb);
@@ -2028,6 +2060,10 @@ int dh_debug_trunk(dh_handle* h, const float* x, int B, int op, void* ws, size_t
     return fail(DH_EINVAL, "dh_debug_trunk: this config's local energy goes envelope first and maps no orbital "
                            "features F over the channel rows");
   // keep_h: the chain form writes the last layer's h too (the production path skips it)
+  if (op != 1 && w.route.det_in_chain) {  // the production launch (log psi into w.logpsi), F kept as well
+    const ChainDet det = chain_det(h, x, B, w.logpsi, McmcEpi{});
+    return run_trunk(h, x, B, 1, w, (hipStream_t)stream, false, /*keep_h=*/true, &det, /*keep_F=*/true);
+  }
   return run_trunk(h, x, B, op == 1 ? h->d.C : 1, w, (hipStream_t)stream, false, /*keep_h=*/true);
 }
 
@@ -2121,6 +2157,16 @@ int dh_debug_gemm_lnch(int N, int mode, const float* X, const uint16_t* Wp, int 
 
 // which fused channel-tail kernel the local energy uses (DH_LNCH at start-up): tests only
 int dh_debug_set_lnch_form(int form) { return set_lnch_form(form); }
+
+// whether a log-psi pass runs the value kernel's work in its last chain launch where the route
+// allows it (1, the default) or always as a launch of its own (0): tests only
+int dh_debug_set_det_in_chain(int on) { return set_det_in_chain(on); }
+
+int dh_debug_det_in_chain(const dh_handle* h, int B, int op) {
+  if (!h || h->analytic() || B < 1) return fail(DH_EINVAL, "bad route query");
+  const int C = op == 1 ? h->d.C : 1;
+  return trunk_route(h->d, h->gemm_mode, C, B * h->d.N * C).det_in_chain;
+}
 
 int dh_debug_gemm_ln(int mode, int bm, const float* X, int ldx, const float* Wt, int ldw, const float* bias,
                      const float* ln, float* h, int rows, int K, void* stream) {

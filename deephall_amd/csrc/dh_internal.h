@@ -101,13 +101,46 @@ struct TrunkRoute {
   int qkv_gemm;      // layers >= 2: a q|k|v GEMM precedes attention (a chained layer's last pass wrote it already)
   int orbital;       // OrbitalMap
   int det;           // DetStage
+  // Not among the fields dh_debug_route reports (kTrunkRouteFields): the value kernel's work can
+  // run as the tail of the last layer's chain launch (gemm_x6.hip chain_x6s_kernel<-1>;
+  // value_pass takes it up, every other caller of run_trunk keeps F in HBM and the value kernel)
+  int det_in_chain;
 };
 constexpr int kTrunkRouteFields = 12;
-static_assert(sizeof(TrunkRoute) == kTrunkRouteFields * sizeof(int), "dh_debug_route copies the fields as ints");
+static_assert(sizeof(TrunkRoute) == (kTrunkRouteFields + 1) * sizeof(int) &&
+                  offsetof(TrunkRoute, det_in_chain) == kTrunkRouteFields * sizeof(int),
+              "dh_debug_route copies the first kTrunkRouteFields fields as ints");
 // The family a dense GEMM of this network takes: split-bf16 if wanted and D allows it, else exact f32
 int gemm_family(const Dims& d, bool want_x6);
 // gemm_mode: DH_GEMM_*; C = 1 or 2N + 5; rows = walkers * N * C
 TrunkRoute trunk_route(const Dims& d, int gemm_mode, int C, int rows);
+// Process-global switch of TrunkRoute::det_in_chain (1 = on where the route allows it, the
+// default; 0 = the separate value kernel everywhere); returns the previous value
+int set_det_in_chain(int on);
+
+// The chain kernel's tile (gemm_x6.hip): 96 rows, and the bytes of its three activation planes
+// in LDS, which are dead after the last GEMM pass (the determinant tail's F tile and walker
+// regions live there)
+constexpr int kChainTileRows = 96;
+constexpr size_t kChainPlaneBytes = 3 * (size_t)kChainTileRows * 264 * 2;
+// det_value_kernel's LDS floats per walker (+1: the epilogue's log psi slot after the f64 unit vectors)
+inline int det_value_per(const Dims& d) {
+  return (2 * d.N * d.M + 2 * d.N * d.N + 2 * d.N + 2 * d.K + 2 + 4 + 6 * d.N + 2 + 3 + 1) & ~3;
+}
+// launch_det_value takes the form with two walkers per wave (one per 32-lane half)
+inline bool det_value_half_wave(const Dims& d) {
+  const int mgv = (d.M + 64 / d.N - 1) / (64 / d.N);  // harmonics per lane
+  return mgv <= 2 && d.N * d.N <= 64;
+}
+// Row stride (floats) of the F tile the chain's determinant tail keeps in LDS.  The contraction
+// reads, per 32-lane half, entry (i, j) of the matrix in lane i N + j at float i ld + j K + k
+// (+ m N K for harmonic m, the same for every lane), and ds_read_b32 banks are float % 32 per
+// half: with ld = orb_cols (192 at N = 6) every row i starts on bank 0 and the read is N-way
+// conflicted.  The smallest ld >= orb_cols with ld % 32 == N K % 32 puts lane i N + j on bank
+// (i N + j) K + k: conflict-free at K = 1, K-way at K determinants.
+inline int det_chain_ldf(const Dims& d) {
+  return d.orb_cols + (((d.N * d.K - d.orb_cols) % 32) + 32) % 32;
+}
 
 constexpr int kRowPad = 256;
 // walker-row buffers (h, qkv, o, t) are padded to 768 = lcm(96, 256) rows, so the log-psi
@@ -212,12 +245,15 @@ void launch_gemm_lnch(int N, const float* X, const uint16_t* Wp, int ldp, const 
 void launch_l1_basis(const Dims& d, const float* W0, const float* UT, const float* bol, const float* ln1,
                      const float* Wm, const float* bm, float* BT, float* VT, hipStream_t s);
 bool chain_attn_supported(int N, int H, int dh);
+struct ChainDet;
 // Log-psi layer tail in one launch (D = K = 256): h1 = LN1(h + X1 Wol + b1) (feature
 // residual when feat.W0), h = LN2(h1 + tanh(h1 Wm + b2)), then Y3 = h W3 + b3 if Wp3.
+// det (TrunkRoute::det_in_chain, Y3 = the orbitals F): the value kernel's work runs as the
+// launch's tail on the tile's F rows in LDS; store_F then says whether F is written to Y3 too.
 void launch_chain_x6(const float* X1, const uint16_t* Wp1, int ldp1, const float* b1, const float* ln1,
                      const uint16_t* Wp2, int ldp2, const float* b2, const float* ln2, const uint16_t* Wp3, int ldp3,
                      const float* b3, int n3, float* Y3, int ldy3, float* h, int rows, X6Feat feat, hipStream_t s,
-                     bool store_h = true);
+                     bool store_h = true, const ChainDet* det = nullptr, bool store_F = true);
 // dst[c][r] = src[r][c] for r < rows, c < cols (row strides ld_src / ld_dst).
 void launch_transpose(const float* src, int ld_src, int rows, int cols, float* dst, int ld_dst, hipStream_t s);
 
@@ -290,6 +326,18 @@ struct McmcEpi {
 };
 void launch_det_value(const Dims& d, const float* F, const float* x, const float* jastrow, const float* norm,
                       float* logpsi, int nw, hipStream_t s, const McmcEpi& epi = McmcEpi{});
+// launch_det_value's arguments for the chain launch that runs the value kernel's body as its
+// tail (launch_chain_x6's det; det_value_half_wave(d) and the route's conditions hold)
+struct ChainDet {
+  const float* x = nullptr;
+  const float* jastrow = nullptr;
+  const float* norm = nullptr;
+  float* logpsi = nullptr;
+  int N = 0, n_up = 0, M = 0, K = 0, nw = 0;
+  int per = 0;  // det_value_per
+  int ldf = 0;  // det_chain_ldf
+  McmcEpi epi;
+};
 // phic != nullptr (det_precontract(d)): the channel matrices are first contracted from F by
 // env_contract_kernel into phic [nw][K][C][N][N] complex, then assembled from there
 // NetObs estimators (netobs.hip): theta / pair-angle histograms, LLL monopole harmonics

@@ -31,6 +31,7 @@
 #include "attn_val.h"
 #include "dh_internal.h"
 #include "device_common.h"
+#include "det_value.h"
 
 #ifndef CHAIN_STAMP  // diagnostic builds only (tools/chain_stamp.py): per-tile phase stamps of chain_x6s
 #define CHAIN_STAMP 0
@@ -1174,6 +1175,10 @@ struct ChainArgs {
   int rows;
   X6Feat feat;
   int store_h;  // 0: P2's h is not written back (the last layer: only P3's orbitals are consumed)
+  // chain_x6s_kernel<kChainDet> only (TrunkRoute::det_in_chain): P3's orbitals stay in LDS for the
+  // value kernel's body, run as the launch's tail; store_F: they are written to Y3 as well
+  int store_F;
+  ChainDet det;
 };
 
 // ---- chained layer tail, pre-split activations ------------------------------------------------
@@ -1193,6 +1198,7 @@ constexpr int CS_NW = 8, CS_RB = CH_BM / 32, CS_PD = 4, CS_LSP = 264;  // plane 
 constexpr int CS_PRMF = 5 * 256;
 constexpr size_t CS_PLANE = (size_t)CH_BM * CS_LSP * 2, CS_SMEM = 3 * CS_PLANE + 2 * CS_NW * CH_BM * 4 + CS_PRMF * 4;
 static_assert(CS_SMEM <= 163840, "chain LDS");
+static_assert(CH_BM == kChainTileRows && 3 * CS_PLANE == kChainPlaneBytes, "trunk_route's LDS bound of the determinant tail");
 
 // 4 f32 -> three packed bf16 pairs per term (as split3)
 __device__ __forceinline__ void split4(const float4& x, uint2& h, uint2& m, uint2& l) {
@@ -1219,8 +1225,19 @@ __device__ __forceinline__ void split4(const float4& x, uint2& h, uint2& m, uint
 // so their LDS round trips overlap (round 5: the scores from the features through the head's
 // 5 x 5 form Mqk, no q / k rows), staging the weights in LDS that the planes overwrite
 // afterwards, the o values held in registers (48 per lane) until every wave is done.
-template <int NA = 0>
+// DET (NAT = kChainDet: chain_x6s_kernel<-1>; NA = 0, the last layer, TrunkRoute::det_in_chain):
+// P3 is the orbital map in one pass (n3 <= 256) and the value kernel's body (det_value.h) runs as the launch's tail on the tile's
+// F rows, kept in the dead planes: the tile's rows are 96 / N whole walkers, walker pair p of the
+// tile goes to wave p % 8 (one walker per 32-lane half, as det_value_kernel<0, true>), every
+// wave in its own two LDS regions.  The tail reads x and (with the MCMC epilogue) writes x,
+// x2, geo, lp, nacc of the tile's own walkers only, and nothing else in this launch reads x or
+// x2 (geo: P1's feature residual reads the tile's own rows, before the tail), so no tile sees
+// another's writes.
+constexpr int kChainDet = -1;
+template <int NAT = 0>
 __global__ __launch_bounds__(512) void chain_x6s_kernel(ChainArgs a) {
+  constexpr bool DET = NAT == kChainDet;
+  constexpr int NA = DET ? 0 : NAT;
   constexpr int RB = CS_RB, PD = CS_PD, LSP = CS_LSP;
   using K16 = std::integral_constant<int, CH_K / 16>;                     // a 256-deep pass
   using KP1 = std::integral_constant<int, (NA > 0 ? CH_KO / 16 : CH_K / 16)>;  // P1: o~ (layer 1) or o
@@ -1737,6 +1754,63 @@ __global__ __launch_bounds__(512) void chain_x6s_kernel(ChainArgs a) {
   if (!a.Wp3) return;
   lbar();
   CHAIN_T(9);
+  if constexpr (DET) {
+    const bool mine = 32 * wid < a.n3;  // wave-uniform; a wave past n3 idles
+    if (mine) gemm(Tr{}, K16{}, Zero{});
+    CHAIN_T(10);
+    lbar();  // every wave is past its reads of the planes: the F tile and the walker regions overwrite them
+    // F tile [96][ldf] floats at the start of the planes, then 16 walker regions of `per` floats.
+    // ldf = det_chain_ldf (dh_internal.h): ldf % 32 == N K % 32, so that the contraction's 32
+    // lanes (entry (i, j) at i ldf + j K + k) fall on distinct banks instead of all rows on one
+    float* Ft = reinterpret_cast<float*>(smem);
+    // the lane index afresh (volatile: not hoisted): tid, l32 and lh kept live across the GEMM
+    // passes for the tail cost 20 B of scratch per lane
+    int tl;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(tl));
+    const int t32 = tl & 31, th = tl >> 5;
+    // The tail's arguments are read from the kernel-argument segment here, through a pointer the
+    // compiler cannot see through, not at entry: held in SGPRs across the three GEMM passes they
+    // spilled (9 SGPRs and, for their lanes, 4 VGPRs: 20 B of scratch per lane)
+    using KArg = const __attribute__((address_space(4))) char;
+    KArg* kp = (KArg*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    const ChainDet det = *(const ChainDet*)(kp + offsetof(ChainArgs, det));
+    const int ldf = det.ldf;
+    if (mine) {
+      // D[tile row][column]: reg q of acc[rb] = row 32 rb + (q & 3) + 8 (q >> 2) + 4 lh, column l32
+      const int c = 32 * wid + t32;
+      const bool cok = c < a.n3;
+      const float bv = cok ? a.b3[c] : 0.f;
+      if (cok) {
+        float* fc = Ft + 4 * th * ldf + c;
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) {
+#pragma unroll
+          for (int q = 0; q < 16; ++q) fc[(32 * rb + (q & 3) + 8 * (q >> 2)) * ldf] = acc[rb][q] + bv;
+        }
+      }
+    }
+    lbar();  // the one barrier between the F tile and the tail
+    CHAIN_T(11);
+    if (a.store_F) {  // F to HBM as well (dh_debug_trunk), from the tile
+      const int nrow = min(CH_BM, rows - row0);
+      for (int i = 64 * wid + tl; i < nrow * a.n3; i += 512) {
+        const int r = i / a.n3, c = i - r * a.n3;
+        a.Y3[(size_t)(row0 + r) * a.ldy3 + c] = Ft[r * ldf + c];
+      }
+    }
+    const int N = det.N, WT = CH_BM / N, w0 = bid * WT;  // walkers per tile (even), the tile's first
+    float* reg = Ft + CH_BM * ldf + (2 * wid + th) * det.per;
+    for (int pr = wid; 2 * pr < WT; pr += CS_NW) {  // wave-uniform trip count
+      const int bw0 = w0 + 2 * pr;
+      if (bw0 >= det.nw) break;  // no walker left for this pair (the stand-alone grid ends there)
+      WaveSync{}();  // the regions are free again (N < 6: more than one pair per wave)
+      det_value_body<0, true>(reg, FRowsTile{Ft, ldf, N, w0}, det.x, det.jastrow, det.norm, det.logpsi, N, det.n_up,
+                              det.M, det.K, bw0 + th, det.nw, t32, det.epi, WaveSync{});
+    }
+    CHAIN_T(12);
+    return;
+  }
   // ---- P3: Y3 = h2 W3 + b3, 256-column passes (a wave past n3 idles), MFMA-layout stores
   for (int col0 = 0; col0 < a.n3; col0 += CH_BN) {
     if (col0 + 32 * wid >= a.n3) continue;  // wave-uniform
@@ -1778,7 +1852,6 @@ __global__ __launch_bounds__(512) void chain_x6s_kernel(ChainArgs a) {
     if (col0 < 3 * CH_BN) CHAIN_T(11 + 2 * (col0 / CH_BN));
   }
 }
-
 
 }  // namespace
 
@@ -1952,9 +2025,11 @@ bool launch_gemm_x6_ln(const float* X, int ldx, const uint16_t* Wp, int ldp, con
 void launch_chain_x6(const float* X1, const uint16_t* Wp1, int ldp1, const float* b1, const float* ln1,
                      const uint16_t* Wp2, int ldp2, const float* b2, const float* ln2, const uint16_t* Wp3, int ldp3,
                      const float* b3, int n3, float* Y3, int ldy3, float* h, int rows, X6Feat feat, hipStream_t s,
-                     bool store_h) {
-  ChainArgs a{X1, Wp1, Wp2, Wp3, ldp1, ldp2, ldp3, b1, ln1, b2, ln2, b3, n3, ldy3, Y3, h, rows, feat, store_h ? 1 : 0};
+                     bool store_h, const ChainDet* det, bool store_F) {
+  ChainArgs a{X1, Wp1, Wp2, Wp3, ldp1, ldp2, ldp3, b1, ln1, b2, ln2, b3, n3, ldy3, Y3, h, rows, feat, store_h ? 1 : 0,
+              store_F ? 1 : 0, det ? *det : ChainDet{}};
   auto k = chain_x6s_kernel<0>;
+  if (det) k = chain_x6s_kernel<kChainDet>;  // trunk_route's conditions: no attention prologue, n3 <= 256
   if (feat.W0qkv) {  // chain_attn_supported(feat.N, 4, 64) checked by the caller
     switch (feat.N) {
       case 2: k = chain_x6s_kernel<2>; break;

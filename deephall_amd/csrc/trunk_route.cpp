@@ -1,8 +1,15 @@
 // Which launches make up one Psiformer pass: the one place that decides (dh_internal.h TrunkRoute;
 // DESIGN.md §1 "Routes" tabulates what comes out, tests/test_abi_host.py pins it).  Host only.
+#include <atomic>
+
 #include "dh_internal.h"
 
 namespace dh {
+
+namespace {
+std::atomic<int> g_det_in_chain{1};
+}
+int set_det_in_chain(int on) { return g_det_in_chain.exchange(on ? 1 : 0); }
 
 int gemm_family(const Dims& d, bool want_x6) {
   const bool nt = d.D % 32 == 0;  // derive_weights keeps the transposed weights and their planes
@@ -82,6 +89,16 @@ TrunkRoute trunk_route(const Dims& d, int gemm_mode, int C, int rows) {
   r.input_h = !r.h0_epilogue;
   // log psi with nothing but the geometry to write: the MCMC proposal has written it already
   r.input_skip = !channels && r.h0_epilogue;
+  // log psi whose last layer is a chain launch (chain_x6s_kernel<0>) with the orbital map as its
+  // last pass: the value kernel's work runs as that launch's tail, on F rows still in LDS, when
+  // the value kernel would take its two-walkers-per-wave form (each of the tile's 8 waves then
+  // owns whole walker pairs: 96 / N is even for every N that form takes), the tile holds whole
+  // walkers, the orbital map is one 256-column pass (a second pass would still read the planes
+  // the F tile overwrites) and the F tile and the 16 walker regions fit the dead planes
+  const int last_form = d.L > 1 ? r.form1 : r.form0;
+  r.det_in_chain = g_det_in_chain.load() && !channels && d.L > 0 && last_form == LF_CHAIN && r.orbital == ORB_IN_CHAIN &&
+                   det_value_half_wave(d) && kChainTileRows % d.N == 0 && d.orb_cols <= 256 &&
+                   (size_t)kChainTileRows * det_chain_ldf(d) * 4 + 16 * (size_t)det_value_per(d) * 4 <= kChainPlaneBytes;
   return r;
 }
 

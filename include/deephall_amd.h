@@ -427,7 +427,10 @@ int dh_kinetic_from_derivatives(const double* x, const double* grad, const doubl
  *   6 MCMC proposal/accept; 7-10 = classes 0-3 launched with 2N+5 channels
  *   (local energy); 11 = layer 1 of the local energy in one launch (gemm_lnch MODE 2:
  *   LayerNorms, tanh and three 32-deep products).  out holds 4 * 12 doubles.
- *   Synchronises on the recorded events. */
+ *   Synchronises on the recorded events.
+ *   A class is timed by events around its launches, so while recording is on a log-psi pass
+ *   launches the value kernel (class 4) on its own even where it would otherwise run as the tail
+ *   of the last chain launch (dh_debug_det_in_chain); the results are bit-identical. */
 int dh_profile_enable(dh_handle* h, int on);
 int dh_profile_read(dh_handle* h, double* out, int reset);
 
@@ -511,6 +514,17 @@ int dh_debug_gemm_x6_choice(int rows, int ncols);
  *     3 envelope first (PhiC from h, no F)
  * DH_EINVAL (negative) for a Laughlin handle or B < 1. */
 int dh_debug_route(const dh_handle* h, int B, int op, int* out, int n);
+/* Test hooks of the determinant tail: where a log-psi pass ends in a chain launch that maps the
+ * orbitals (route fields 5 = 2, 10 = 2) and the value kernel would put two walkers on a wave
+ * (N = 6 at 2Q = 15), that launch runs the value kernel's work as its tail on orbital rows still in
+ * the CU (gemm_x6.hip), and no value kernel is launched; bit-identical results.
+ * dh_debug_set_det_in_chain(0) makes every later pass of the process launch the value kernel on
+ * its own instead (1: the default); it returns the previous setting.
+ * dh_debug_det_in_chain: 1 if a pass of B walkers (op as dh_debug_route) carries the tail under
+ * the current setting, else 0 (a pass run while dh_profile_enable records launches the value
+ * kernel on its own all the same); host only; DH_EINVAL (negative) as dh_debug_route. */
+int dh_debug_set_det_in_chain(int on);
+int dh_debug_det_in_chain(const dh_handle* h, int B, int op);
 int dh_debug_x6_plane_rows(int ncols);
 int dh_debug_split_planes(const float* Wt, int ldw, int ncols, int K, uint16_t* Wp, void* stream);
 int dh_debug_gemm_x6(int variant, const float* X, int ldx, const uint16_t* Wp, int ldp, const float* bias,
