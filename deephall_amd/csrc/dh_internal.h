@@ -1,4 +1,4 @@
-// Internal declarations shared by the HIP kernel files and the C ABI (api.cpp).
+// Internal declarations shared by the HIP kernel files and the C ABI (api.cpp, api_grad.cpp).
 #pragma once
 #include <algorithm>
 #include <hip/hip_runtime.h>
@@ -456,7 +456,7 @@ void launch_pfaffian(const Dims& d, const float* x, int p, float* logpsi, float*
 void launch_det_bwd(const Dims& d, const float* F, const float* x, const float* jastrow, const float* norm,
                     const float* ct, float* dF, float* jg, int nw, hipStream_t s);
 
-// kfac.hip: KFAC curvature statistics, damped inverses and update (api.cpp dh_kfac_*)
+// kfac.hip: KFAC curvature statistics, damped inverses and update (api_grad.cpp dh_kfac_*)
 struct KfacSlot {  // one factor matrix n x n (f32) at float offset `off` of the statistics buffer
   int n;
   size_t off;
@@ -509,7 +509,7 @@ void launch_kfac_precondition(const KfacDevPlan& p, const float* grad, const flo
 void launch_kfac_update(float* params, const float* pg, size_t n, double* info, double lr, double norm_constraint,
                         hipStream_t s);
 
-// ntk.hip: the per-walker gradient Gram matrix (api.cpp dh_ntk)
+// ntk.hip: the per-walker gradient Gram matrix (api_grad.cpp dh_ntk)
 constexpr int kNtkTileRows = 128;  // rows (walkers x n) of one Gram tile
 int ntk_tile_walkers(int n);       // whole walkers of n rows per tile
 // T[b][b'] (nwalk x nwalk) += sum_{t in b, t' in b'} (X_t . X_t' + a_t + a_t') (Y_t . Y_t'), rows t

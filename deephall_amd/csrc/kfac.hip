@@ -2,7 +2,7 @@
 // the reference's default optimizer (deephall/optimizers/kfac.py:195-241 on kfac_jax; the
 // algorithm restated in oracle/kfac.py and DESIGN.md §3d).
 //
-// Per iteration (api.cpp dh_kfac_vjp / dh_kfac_step):
+// Per iteration (api_grad.cpp dh_kfac_vjp / dh_kfac_step):
 //   statistics   A = x~^T x~ / rows and G = dy^T dy / rows of every dense layer from the
 //                saved forward activations and a second reverse pass with the Fisher
 //                cotangent sqrt(2) on Re log psi (tn_partial X^T X, exact-f32 MFMA, chunk

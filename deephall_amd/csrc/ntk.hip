@@ -1,5 +1,5 @@
 // The per-walker gradient Gram matrix (the neural tangent kernel of log psi) that MinSR solves
-// in sample space (api.cpp dh_ntk):
+// in sample space (api_grad.cpp dh_ntk):
 //
 //   T[b][b'] = <g_b, g_b'>,  g_b = ct_b.re d Re log psi_b / dp + ct_b.im d Im log psi_b / dp
 //

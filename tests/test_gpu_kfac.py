@@ -93,7 +93,7 @@ def test_kfac_statistics_match_oracle(cuda, name, B, layers, orbital):
 def test_kfac_vjp_with_cotangent_and_chunks(cuda):
     """The training path of dh_kfac_vjp: a real cotangent (the gradient's and the
     Fisher pass share one saved forward) and walker chunks (the statistics accumulated across
-    chunks, api.cpp's kf.acc).  The statistics equal the ct=None single-chunk result, the
+    chunks, api_grad.cpp's acc).  The statistics equal the ct=None single-chunk result, the
     returned gradient equals model.vjp's, and the chunked run equals the unchunked one."""
     from deephall_amd.networks import psiformer as pf
 
