@@ -95,7 +95,13 @@ EXPORTS = [
     "dh_ntk_jvp",
     "dh_fidelity_partial",
     "dh_fidelity_residual",
+    "dh_swap_classify",
+    "dh_swap_compact",
+    "dh_swap_reduce",
+    "dh_swap_workspace_bytes",
 ]
+
+DH_SWAP_MAX_ANGLES = 64
 
 DH_NFID = 5  # dh_fidelity_partial: m, S re, S im, S2, n
 
@@ -252,6 +258,15 @@ def load(path: Path | str | None = None):
     lib.dh_fidelity_partial.restype = i32
     lib.dh_fidelity_residual.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.dh_fidelity_residual.restype = i32
+    pf = C.POINTER(C.c_float)  # the cap angles: a host array
+    lib.dh_swap_classify.argtypes = [vp, i32, i32, i32, i32, pf, i32, vp, vp, vp]
+    lib.dh_swap_classify.restype = i32
+    lib.dh_swap_compact.argtypes = [vp, i32, i32, i32, i32, pf, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.dh_swap_compact.restype = i32
+    lib.dh_swap_reduce.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.dh_swap_reduce.restype = i32
+    lib.dh_swap_workspace_bytes.argtypes = [i32, i32]
+    lib.dh_swap_workspace_bytes.restype = sz
     lib.dh_grad_cotangent.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.dh_grad_cotangent.restype = i32
     lib.dh_adam_update.argtypes = [vp, vp, vp, vp, sz, f32, f32, f32, f32, i32, vp]

@@ -1198,6 +1198,62 @@ int dh_monopole_orbitals(const float* points, int n, int flux, float* out, void*
   return check_launch();
 }
 
+// ---- Renyi-2 swap estimator (swap.hip): no handle, like the histograms ----
+
+namespace {
+// the checks the four swap calls share; thetas == nullptr: the call takes no angles
+const char* swap_args_error(int B, int nelec, int n_up, int n_dn, const float* thetas, int A) {
+  if (B < 2) return "swap: B < 2 (no pair)";
+  if (nelec < 1 || n_up < 0 || n_dn < 0 || n_up + n_dn != nelec) return "swap: n_up + n_dn != nelec or nelec < 1";
+  if (A < 1 || A > kSwapMaxAngles) return "swap: A outside 1..DH_SWAP_MAX_ANGLES";
+  if ((int64_t)2 * A * (B / 2) > INT32_MAX) return "swap: 2 A (B / 2) >= 2^31";
+  if (((int64_t)n_up + 1) * ((int64_t)n_dn + 1) > INT32_MAX / A) return "swap: A (n_up + 1)(n_dn + 1) >= 2^31";
+  for (int a = 0; thetas && a < A; ++a)
+    if (thetas[a] != thetas[a]) return "swap: a theta is NaN";
+  return nullptr;
+}
+SwapThetas swap_thetas(const float* thetas, int A) {
+  SwapThetas th{};
+  for (int a = 0; a < A; ++a) th.t[a] = thetas[a];
+  return th;
+}
+}  // namespace
+
+size_t dh_swap_workspace_bytes(int B, int A) {
+  if (swap_args_error(B, 1, 1, 0, nullptr, A)) return 0;
+  return align64((size_t)A * (B / 2) * sizeof(int32_t));
+}
+
+int dh_swap_classify(const float* x, int B, int nelec, int n_up, int n_dn, const float* thetas, int A,
+                     int32_t* sector, int32_t* counts, void* stream) {
+  if (!x || !thetas || !sector || !counts) return fail(DH_EINVAL, "swap: null pointer");
+  if (const char* e = swap_args_error(B, nelec, n_up, n_dn, thetas, A)) return fail(DH_EINVAL, e);
+  launch_swap_classify(x, B, nelec, n_up, swap_thetas(thetas, A), A, sector, counts, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_swap_compact(const float* x, int B, int nelec, int n_up, int n_dn, const float* thetas, int A,
+                    const int32_t* sector, int32_t* start, int32_t* pair, float* xs, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  if (!x || !thetas || !sector || !start || !pair || !xs || !workspace) return fail(DH_EINVAL, "swap: null pointer");
+  if (const char* e = swap_args_error(B, nelec, n_up, n_dn, thetas, A)) return fail(DH_EINVAL, e);
+  if (workspace_bytes < dh_swap_workspace_bytes(B, A)) return fail(DH_ENOMEM, "workspace too small");
+  launch_swap_compact(x, B, nelec, n_up, swap_thetas(thetas, A), A, sector, (int32_t*)workspace, start, pair, xs,
+                      (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_swap_reduce(const float* logpsi, const float* logpsi_s, int B, int nelec, int n_up, int n_dn, int A, int M,
+                   const int32_t* pair, const int32_t* sector, const int32_t* start, double* sums, void* stream) {
+  if (!logpsi || !sector || !start || !sums || (M != 0 && (!logpsi_s || !pair)))
+    return fail(DH_EINVAL, "swap: null pointer");
+  if (const char* e = swap_args_error(B, nelec, n_up, n_dn, nullptr, A)) return fail(DH_EINVAL, e);
+  if (M < 0 || (int64_t)M > (int64_t)A * (B / 2)) return fail(DH_EINVAL, "swap: M outside 0..A (B / 2)");
+  launch_swap_reduce(logpsi, logpsi_s, B, (n_up + 1) * (n_dn + 1), A, M, pair, sector, start, sums,
+                     (hipStream_t)stream);
+  return check_launch();
+}
+
 // ---- log psi supplied by the caller (arbitrary callables, mcmc.py:105 / hamiltonian.py:83) ----
 
 int dh_mh_init(const float* logpsi, float* lp, int32_t* n_accept, int B, void* stream) {

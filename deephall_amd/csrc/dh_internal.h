@@ -343,6 +343,21 @@ struct ChainDet {
 // NetObs estimators (netobs.hip): theta / pair-angle histograms, LLL monopole harmonics
 void launch_histograms(const float* x, int B, int N, int db, int pb, float* dens, float* pair, hipStream_t s);
 void launch_monopole_orbitals(const float* pts, int n, int flux, float* out, hipStream_t s);
+// Renyi-2 swap estimator (swap.hip): classify pairs by their counts in the caps theta < t[a],
+// compact the matched ones (scan + gather of the swapped rows), reduce the swap values by angle
+// and sector.  The cap angles travel as a kernel argument.  B >= 2, 1 <= A <= kSwapMaxAngles and
+// 2 A (B / 2) < 2^31 are the callers' to check: then no grid is empty.
+constexpr int kSwapMaxAngles = 64;
+struct SwapThetas {
+  float t[kSwapMaxAngles];
+};
+void launch_swap_classify(const float* x, int B, int N, int n_up, const SwapThetas& th, int A, int32_t* sector,
+                          int32_t* counts, hipStream_t s);
+// row [A (B / 2)]: workspace (each pair's output row, -1 when unmatched)
+void launch_swap_compact(const float* x, int B, int N, int n_up, const SwapThetas& th, int A, const int32_t* sector,
+                         int32_t* row, int32_t* start, int32_t* pair, float* xs, hipStream_t s);
+void launch_swap_reduce(const float* logpsi, const float* logpsi_s, int B, int K, int A, int M, const int32_t* pair,
+                        const int32_t* sector, const int32_t* start, double* sums, hipStream_t s);
 bool det_precontract(const Dims& d);
 void launch_det_energy(const Dims& d, const float* F, const float* x, const float* geo, const float* jastrow,
                        const float* norm, float* e_l, float* obs, int nw, hipStream_t s, float* phic);

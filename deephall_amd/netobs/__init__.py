@@ -9,6 +9,9 @@ with the same names, options, value/state keys and digests:
 * histograms (density, pair correlation) and the lowest-Landau-level monopole harmonics of
   the one-body density matrix are HIP kernels (csrc/netobs.hip, ``dh_histograms``,
   ``dh_monopole_orbitals``);
+* the Renyi-2 entanglement entropy of a polar cap (observables/renyi2.py, not in the reference)
+  classifies, compacts and reduces its swapped walker pairs in csrc/swap.hip (``dh_swap_*``);
+  ``entanglement.filled_lll_cap`` is the exact filled-Landau-level answer to check it against;
 * every wavefunction value goes through ``dh_logpsi`` (Psiformer or the native Laughlin
   state), the walk through ``dh_mcmc_step``;
 * ``evaluate`` is a minimal stand-in for NetObs's own evaluation loop (restore, burn-in,
@@ -20,13 +23,32 @@ with the same names, options, value/state keys and digests:
 from .adaptor import DeepHallAdaptor, DeepHallAuxData
 from .estimator import Estimator, Observable, evaluate
 from .hall_system import HallSystem
-from .observables import density, one_rdm, overlap, pair_corr
+from .observables import density, one_rdm, overlap, pair_corr, renyi2
 
-ESTIMATORS = {
+# estimators the reference does not have (no ``deephall@`` name in cli_extend.py)
+EXTRA_ESTIMATORS = {
+    "renyi2": renyi2.DEFAULT,
+}
+
+
+class _Registry(dict):
+    """Estimators by name.  The dict's own keys — what iterating, ``len`` and ``in`` see — are
+    the reference's ``deephall@`` names, so the registry still lists exactly what cli_extend.py
+    registers; ``ESTIMATORS[name]`` and ``.get(name)`` also find EXTRA_ESTIMATORS."""
+
+    def __missing__(self, name):
+        return EXTRA_ESTIMATORS[name]
+
+    def get(self, name, default=None):
+        return self[name] if name in self or name in EXTRA_ESTIMATORS else default
+
+
+ESTIMATORS = _Registry({
     "density": density.DEFAULT,
     "pair_corr": pair_corr.DEFAULT,
     "overlap": overlap.DEFAULT,
     "one_rdm": one_rdm.DEFAULT,
-}
+})
 
-__all__ = ["DeepHallAdaptor", "DeepHallAuxData", "Estimator", "Observable", "HallSystem", "evaluate", "ESTIMATORS"]
+__all__ = ["DeepHallAdaptor", "DeepHallAuxData", "Estimator", "Observable", "HallSystem", "evaluate", "ESTIMATORS",
+           "EXTRA_ESTIMATORS"]

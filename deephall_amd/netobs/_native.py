@@ -2,6 +2,8 @@
 
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from .. import _lib
@@ -34,3 +36,76 @@ def monopole_orbitals(points: torch.Tensor, flux: int) -> torch.Tensor:
     lib = _lib.load()
     _lib.check(lib.dh_monopole_orbitals(_ptr(flat), flat.shape[0], int(flux), _ptr(out), _stream(pts.device)))
     return torch.view_as_complex(out).reshape(*shape, flux + 1)
+
+
+# ---- Renyi-2 swap estimator (csrc/swap.hip) ----------------------------------------------------
+
+def _swap_args(x: torch.Tensor, thetas, nspins):
+    x = _check_cuda(x)
+    B, N, _ = x.shape
+    n_up, n_dn = int(nspins[0]), int(nspins[1])
+    th = [float(t) for t in thetas]
+    return x, B, N, n_up, n_dn, (C.c_float * len(th))(*th), len(th)
+
+
+def swap_classify(x: torch.Tensor, thetas, nspins):
+    """sector[A, P] int32 (-1: unmatched) and counts[A, K] int32 of pairs (p, p + P), P = B // 2."""
+    x, B, N, n_up, n_dn, th, A = _swap_args(x, thetas, nspins)
+    K = (n_up + 1) * (n_dn + 1)
+    sector = torch.empty(A, B // 2, dtype=torch.int32, device=x.device)
+    counts = torch.zeros(A, K, dtype=torch.int32, device=x.device)
+    lib = _lib.load()
+    _lib.check(lib.dh_swap_classify(_ptr(x), B, N, n_up, n_dn, th, A, _ptr(sector), _ptr(counts), _stream(x.device)))
+    return sector, counts
+
+
+def swap_compact(x: torch.Tensor, thetas, nspins, sector: torch.Tensor):
+    """(M, start[A + 1], pair[M], xs[2 M, N, 2]): the matched pairs' rows and swapped configurations.
+
+    Reads M back from the device (one synchronisation); pair and xs are views of buffers sized for
+    every pair matched."""
+    x, B, N, n_up, n_dn, th, A = _swap_args(x, thetas, nspins)
+    P = B // 2
+    lib = _lib.load()
+    start = torch.empty(A + 1, dtype=torch.int32, device=x.device)
+    pair = torch.empty(A * P, dtype=torch.int32, device=x.device)
+    xs = torch.empty(2 * A * P, N, 2, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(int(lib.dh_swap_workspace_bytes(B, A)), 1), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.dh_swap_compact(_ptr(x), B, N, n_up, n_dn, th, A, _ptr(sector), _ptr(start), _ptr(pair), _ptr(xs),
+                                   _ptr(ws), ws.numel(), _stream(x.device)))
+    M = int(start[A].item())
+    return M, start, pair[:M], xs[:2 * M]
+
+
+def swap_reduce(logpsi: torch.Tensor, logpsi_s: torch.Tensor | None, nspins, M: int, pair, sector, start):
+    """sums[A, K] complex128 from logpsi[B, 2] and logpsi_s[2 M, 2] float32 (dh_logpsi's layout)."""
+    n_up, n_dn = int(nspins[0]), int(nspins[1])
+    A, K = sector.shape[0], (n_up + 1) * (n_dn + 1)
+    logpsi = _check_cuda(logpsi)
+    logpsi_s = _check_cuda(logpsi_s) if M else None
+    sums = torch.empty(A, K, 2, dtype=torch.float64, device=logpsi.device)
+    lib = _lib.load()
+    _lib.check(lib.dh_swap_reduce(_ptr(logpsi), _ptr(logpsi_s), logpsi.shape[0], n_up + n_dn, n_up, n_dn, A, int(M),
+                                  _ptr(pair if M else None), _ptr(sector), _ptr(start), _ptr(sums),
+                                  _stream(logpsi.device)))
+    return torch.view_as_complex(sums)
+
+
+def _log_pairs(lp: torch.Tensor) -> torch.Tensor:
+    """Complex log psi [rows] -> float32 [rows, 2] (re, im), as dh_logpsi writes it."""
+    return torch.view_as_real(lp.to(torch.complex64)).contiguous()
+
+
+def swap_purity(apply, x: torch.Tensor, thetas, nspins):
+    """Swap-estimator sums of walkers x[B, N, 2] paired (p, p + B // 2) over the caps theta < thetas[a].
+
+    ``apply`` gives complex log psi of [rows, N, 2]: one call on x, one batched call on the 2 M
+    swapped rows of the matched pairs (skipped when M = 0).  Returns sums[A, K] complex128 —
+    sums.sum(-1) / (B // 2) estimates Tr rho_A^2 — and counts[A, K] int64, the sector counts of
+    all 2 (B // 2) pair members."""
+    x = _check_cuda(x)
+    sector, counts = swap_classify(x, thetas, nspins)
+    M, start, pair, xs = swap_compact(x, thetas, nspins, sector)
+    logpsi = _log_pairs(apply(x))
+    logpsi_s = _log_pairs(apply(xs)) if M else None
+    return swap_reduce(logpsi, logpsi_s, nspins, M, pair, sector, start), counts.long()

@@ -393,6 +393,49 @@ int dh_histograms(const float* x, int B, int nelec, int density_bins, int pair_b
  * +-(1 - 1e-4) as there). */
 int dh_monopole_orbitals(const float* points, int n, int flux, float* out, void* stream);
 
+/* ---- Renyi-2 entanglement entropy of a spherical cap: the swap estimator ------------------
+ * Walkers x[B][nelec][2] (theta, phi); the slots below n_up are up electrons (n_up + n_dn =
+ * nelec).  P = B / 2 pairs: pair p is (R1, R2) = (walker p, walker p + P), an odd last walker
+ * is ignored.  Region a of A is the cap theta < thetas[a]; thetas is a HOST array (it is
+ * checked and passed by value), 1 <= A <= DH_SWAP_MAX_ANGLES.  "In the cap" is the float32
+ * comparison on the stored theta.  A pair is matched at angle a when the up count and the down
+ * count in the cap agree between R1 and R2; its sector is k = nA_up (n_dn + 1) + nA_dn,
+ * K = (n_up + 1)(n_dn + 1) sectors.  For a matched pair R1' is R1 with the coordinates of its
+ * in-cap slots, in ascending slot order within each spin, replaced by R2's in-cap coordinates
+ * in ascending slot order, and R2' the mirror image (copies of the stored floats).
+ *
+ * dh_swap_classify  sector[A][P] = the pair's sector, -1 when unmatched; ADDS to counts[A][K]
+ *                   the sector of each of the 2 P members (matched or not): their sum grows by
+ *                   2 P per angle.
+ * dh_swap_compact   from sector: the matched pairs in (a-major, then p) order get the rows
+ *                   o = 0..M-1; start[A + 1] = the first row of every angle and start[A] = M (the
+ *                   device int the caller reads); pair[o] = a P + p; xs[2 o] = R1' and
+ *                   xs[2 o + 1] = R2', each [nelec][2].  pair holds A P ints and xs 2 A P rows (the
+ *                   case of every pair matched); only the first M / 2 M are written.  The rows are
+ *                   handed out by a prefix sum, not an atomic counter: the same on every call.
+ *                   workspace: dh_swap_workspace_bytes(B, A) device bytes.
+ * dh_swap_reduce    sums[A][K][2] (re, im; double) = the sum over the matched pairs of angle a in
+ *                   sector k of exp(logpsi_s[2 o] + logpsi_s[2 o + 1] - logpsi[p] - logpsi[p + P]),
+ *                   with logpsi[B][2] of x and logpsi_s[2 M][2] of the first 2 M rows of xs as
+ *                   dh_logpsi writes them, and M as read from start[A] (0 <= M <= A P; with
+ *                   M = 0 logpsi_s and pair are not read and may be null).  Double arithmetic from
+ *                   the float32 logs on, a fixed summation order, no float atomics: two calls give
+ *                   identical bits.  An (a, k) without a matched pair gets zeros.
+ *                   Tr rho_A^2 = sum_k sums[a][k] / P.
+ * Each call checks its arguments before any device call: a null pointer, B < 2, nelec < 1,
+ * n_up < 0, n_dn < 0, n_up + n_dn != nelec, A out of range, a NaN theta or 2 A P >= 2^31 is
+ * DH_EINVAL (dh_swap_workspace_bytes then returns 0).  No dh_handle: like the histogram
+ * kernels these know nothing of the network. */
+#define DH_SWAP_MAX_ANGLES 64
+int dh_swap_classify(const float* x, int B, int nelec, int n_up, int n_dn, const float* thetas, int A,
+                     int32_t* sector, int32_t* counts, void* stream);
+int dh_swap_compact(const float* x, int B, int nelec, int n_up, int n_dn, const float* thetas, int A,
+                    const int32_t* sector, int32_t* start, int32_t* pair, float* xs, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int dh_swap_reduce(const float* logpsi, const float* logpsi_s, int B, int nelec, int n_up, int n_dn, int A, int M,
+                   const int32_t* pair, const int32_t* sector, const int32_t* start, double* sums, void* stream);
+size_t dh_swap_workspace_bytes(int B, int A);
+
 /* ---- log psi supplied by the caller: the arbitrary-callable boundary ---------------------
  * The reference's make_mcmc_step(batch_network, ...) (mcmc.py:105-150) and
  * make_local_kinetic_energy(f, Q, r) (hamiltonian.py:83-172) accept ANY log psi.  For one
