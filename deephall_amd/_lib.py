@@ -99,9 +99,15 @@ EXPORTS = [
     "dh_swap_compact",
     "dh_swap_reduce",
     "dh_swap_workspace_bytes",
+    "dh_rdm_norb",
+    "dh_rdm_workspace_bytes",
+    "dh_monopole_harmonics",
+    "dh_rdm_displace",
+    "dh_rdm_accumulate",
 ]
 
 DH_SWAP_MAX_ANGLES = 64
+DH_RDM_MAX_LEVELS = 4
 
 DH_NFID = 5  # dh_fidelity_partial: m, S re, S im, S2, n
 
@@ -267,6 +273,16 @@ def load(path: Path | str | None = None):
     lib.dh_swap_reduce.restype = i32
     lib.dh_swap_workspace_bytes.argtypes = [i32, i32]
     lib.dh_swap_workspace_bytes.restype = sz
+    lib.dh_rdm_norb.argtypes = [i32, i32]
+    lib.dh_rdm_norb.restype = i32
+    lib.dh_rdm_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    lib.dh_rdm_workspace_bytes.restype = sz
+    lib.dh_monopole_harmonics.argtypes = [vp, i32, i32, i32, vp, vp]
+    lib.dh_monopole_harmonics.restype = i32
+    lib.dh_rdm_displace.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    lib.dh_rdm_displace.restype = i32
+    lib.dh_rdm_accumulate.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+    lib.dh_rdm_accumulate.restype = i32
     lib.dh_grad_cotangent.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.dh_grad_cotangent.restype = i32
     lib.dh_adam_update.argtypes = [vp, vp, vp, vp, sz, f32, f32, f32, f32, i32, vp]

@@ -1254,6 +1254,64 @@ int dh_swap_reduce(const float* logpsi, const float* logpsi_s, int B, int nelec,
   return check_launch();
 }
 
+// ---- Landau-level-resolved one-body density matrix (rdm.hip): no handle either ----
+
+namespace {
+const char* rdm_basis_error(int flux, int levels) {
+  if (levels < 1 || levels > kRdmMaxLevels) return "rdm: levels outside 1..DH_RDM_MAX_LEVELS";
+  if (flux < 0 || flux > 126) return "rdm: flux outside 0..126";
+  return nullptr;
+}
+const char* rdm_size_error(int B, int nelec, int P) {
+  if (B < 1 || P < 1) return "rdm: B < 1 or P < 1";
+  if (nelec < 1 || nelec > 32) return "rdm: nelec outside 1..32";
+  if ((int64_t)P * B > (int64_t)1 << 30) return "rdm: P B > 2^30";
+  if ((int64_t)P * B * nelec * nelec > INT32_MAX) return "rdm: P B nelec^2 >= 2^31";
+  return nullptr;
+}
+}  // namespace
+
+int dh_rdm_norb(int flux, int levels) { return rdm_basis_error(flux, levels) ? 0 : rdm_norb(flux, levels); }
+
+size_t dh_rdm_workspace_bytes(int B, int nelec, int flux, int levels, int P) {
+  if (rdm_basis_error(flux, levels) || rdm_size_error(B, nelec, P)) return 0;
+  return align64(rdm_workspace_bytes((int64_t)P * B, flux, levels));
+}
+
+int dh_monopole_harmonics(const float* points, int n, int flux, int levels, float* out, void* stream) {
+  if (!points || !out) return fail(DH_EINVAL, "rdm: null pointer");
+  if (const char* e = rdm_basis_error(flux, levels)) return fail(DH_EINVAL, e);
+  if (n < 1 || (int64_t)n * (flux + 2 * levels - 1) > INT32_MAX) return fail(DH_EINVAL, "rdm: n < 1 or too large");
+  const double* table = nullptr;
+  HIP_TRY(rdm_table(flux, levels, &table));
+  launch_monopole_harmonics(points, n, flux, levels, table, out, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_rdm_displace(const float* x, const float* r_prime, int B, int nelec, int P, float* xp, void* stream) {
+  if (!x || !r_prime || !xp) return fail(DH_EINVAL, "rdm: null pointer");
+  if (const char* e = rdm_size_error(B, nelec, P)) return fail(DH_EINVAL, e);
+  launch_rdm_displace(x, r_prime, B, nelec, P, xp, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_rdm_accumulate(const float* x, const float* r_prime, const float* logpsi, const float* logpsi_p, int B,
+                      int nelec, int n_up, int flux, int levels, int P, int by_spin, double* rho, int32_t* nvalid,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  if (!x || !r_prime || !logpsi || !logpsi_p || !rho || !nvalid || !workspace)
+    return fail(DH_EINVAL, "rdm: null pointer");
+  if (const char* e = rdm_basis_error(flux, levels)) return fail(DH_EINVAL, e);
+  if (const char* e = rdm_size_error(B, nelec, P)) return fail(DH_EINVAL, e);
+  if (n_up < 0 || n_up > nelec) return fail(DH_EINVAL, "rdm: n_up outside 0..nelec");
+  if (workspace_bytes < dh_rdm_workspace_bytes(B, nelec, flux, levels, P))
+    return fail(DH_EINVAL, "rdm: workspace smaller than dh_rdm_workspace_bytes");
+  const double* table = nullptr;
+  HIP_TRY(rdm_table(flux, levels, &table));
+  HIP_TRY(launch_rdm_accumulate(x, r_prime, logpsi, logpsi_p, B, nelec, n_up, flux, levels, P, by_spin != 0, table,
+                                rho, nvalid, workspace, (hipStream_t)stream));
+  return check_launch();
+}
+
 // ---- log psi supplied by the caller (arbitrary callables, mcmc.py:105 / hamiltonian.py:83) ----
 
 int dh_mh_init(const float* logpsi, float* lp, int32_t* n_accept, int B, void* stream) {

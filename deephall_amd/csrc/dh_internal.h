@@ -358,6 +358,21 @@ void launch_swap_compact(const float* x, int B, int N, int n_up, const SwapTheta
                          int32_t* row, int32_t* start, int32_t* pair, float* xs, hipStream_t s);
 void launch_swap_reduce(const float* logpsi, const float* logpsi_s, int B, int K, int A, int M, const int32_t* pair,
                         const int32_t* sector, const int32_t* start, double* sums, hipStream_t s);
+// Landau-level-resolved one-body density matrix (rdm.hip): the harmonics Y_{Q,Q+n,m} of the levels
+// n < levels, the displaced configurations, and rho = 4 pi sum over samples of u conj(v) reduced on
+// the device in double.  The limits (levels <= kRdmMaxLevels, flux <= 126, nelec <= 32, P B <= 2^30,
+// P B nelec^2 < 2^31) are the callers' to check.  table: rdm_table's device coefficients.
+constexpr int kRdmMaxLevels = 4;
+int rdm_norb(int flux, int levels);
+int rdm_nsplit(int64_t samples, int flux, int levels);
+size_t rdm_workspace_bytes(int64_t samples, int flux, int levels);
+hipError_t rdm_table(int flux, int levels, const double** table);
+void launch_monopole_harmonics(const float* pts, int n, int flux, int levels, const double* table, float* out,
+                               hipStream_t s);
+void launch_rdm_displace(const float* x, const float* r_prime, int B, int N, int P, float* xp, hipStream_t s);
+hipError_t launch_rdm_accumulate(const float* x, const float* r_prime, const float* logpsi, const float* logpsi_p,
+                                 int B, int N, int n_up, int flux, int levels, int P, int by_spin,
+                                 const double* table, double* rho, int32_t* nvalid, void* workspace, hipStream_t s);
 bool det_precontract(const Dims& d);
 void launch_det_energy(const Dims& d, const float* F, const float* x, const float* geo, const float* jastrow,
                        const float* norm, float* e_l, float* obs, int nw, hipStream_t s, float* phic);

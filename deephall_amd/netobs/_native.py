@@ -109,3 +109,79 @@ def swap_purity(apply, x: torch.Tensor, thetas, nspins):
     logpsi = _log_pairs(apply(x))
     logpsi_s = _log_pairs(apply(xs)) if M else None
     return swap_reduce(logpsi, logpsi_s, nspins, M, pair, sector, start), counts.long()
+
+
+# ---- Landau-level-resolved one-body density matrix (csrc/rdm.hip) --------------------------------
+
+def rdm_norb(flux: int, levels: int) -> int:
+    """Orbitals Y_{Q,Q+n,m} of the levels n < levels: levels (flux + 1) + levels (levels - 1)."""
+    norb = int(_lib.load().dh_rdm_norb(int(flux), int(levels)))
+    if norb < 1:
+        raise ValueError(f"ll_rdm: flux {flux} outside 0..126 or levels {levels} outside 1..{_lib.DH_RDM_MAX_LEVELS}")
+    return norb
+
+
+def monopole_harmonics(points: torch.Tensor, flux: int, levels: int) -> torch.Tensor:
+    """Y_{Q,Q+n,m}(points), level-major, m ascending: complex64 [..., norb]; level 0 is monopole_orbitals."""
+    pts = _check_cuda(points)
+    shape = pts.shape[:-1]
+    flat = pts.reshape(-1, 2)
+    norb = rdm_norb(flux, levels)
+    out = torch.empty(flat.shape[0], norb, 2, dtype=torch.float32, device=pts.device)
+    lib = _lib.load()
+    _lib.check(lib.dh_monopole_harmonics(_ptr(flat), flat.shape[0], int(flux), int(levels), _ptr(out),
+                                         _stream(pts.device)))
+    return torch.view_as_complex(out).reshape(*shape, norb)
+
+
+def rdm_displace(x: torch.Tensor, r_prime: torch.Tensor) -> torch.Tensor:
+    """xp[P, B, N, N, 2]: xp[p, b, a] is walker b of x[B, N, 2] with electron a at r_prime[p, b]."""
+    x, r_prime = _check_cuda(x), _check_cuda(r_prime)
+    B, N, _ = x.shape
+    P = r_prime.shape[0]
+    if r_prime.shape != (P, B, 2):
+        raise ValueError(f"rdm_displace: r_prime must be [P, {B}, 2], got {tuple(r_prime.shape)}")
+    xp = torch.empty(P, B, N, N, 2, dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    _lib.check(lib.dh_rdm_displace(_ptr(x), _ptr(r_prime), B, N, P, _ptr(xp), _stream(x.device)))
+    return xp
+
+
+def rdm_accumulate(x: torch.Tensor, r_prime: torch.Tensor, logpsi: torch.Tensor, logpsi_p: torch.Tensor, n_up: int,
+                   flux: int, levels: int, by_spin: bool = False):
+    """(rho[S, norb, norb] complex128, nvalid): the SUM over the kept (walker, point) samples of
+    4 pi u_i conj(v_j) from x[B, N, 2], r_prime[P, B, 2], logpsi[B, 2] and logpsi_p[P B N, 2]
+    float32 (dh_logpsi's layout; rows as rdm_displace orders them).  S = 2 (up, down) when by_spin.
+    nvalid is read back from the device (one synchronisation)."""
+    x, r_prime = _check_cuda(x), _check_cuda(r_prime)
+    logpsi, logpsi_p = _check_cuda(logpsi), _check_cuda(logpsi_p)
+    B, N, _ = x.shape
+    P = r_prime.shape[0]
+    if r_prime.shape != (P, B, 2) or logpsi.shape != (B, 2) or logpsi_p.shape != (P * B * N, 2):
+        raise ValueError(f"rdm_accumulate: shapes {tuple(r_prime.shape)}, {tuple(logpsi.shape)}, "
+                         f"{tuple(logpsi_p.shape)} do not fit x {tuple(x.shape)}")
+    norb, S = rdm_norb(flux, levels), 2 if by_spin else 1
+    lib = _lib.load()
+    rho = torch.empty(S, norb, norb, 2, dtype=torch.float64, device=x.device)
+    nvalid = torch.empty(1, dtype=torch.int32, device=x.device)
+    ws = torch.empty(max(int(lib.dh_rdm_workspace_bytes(B, N, int(flux), int(levels), P)), 1), dtype=torch.uint8,
+                     device=x.device)
+    _lib.check(lib.dh_rdm_accumulate(_ptr(x), _ptr(r_prime), _ptr(logpsi), _ptr(logpsi_p), B, N, int(n_up), int(flux),
+                                     int(levels), P, int(bool(by_spin)), _ptr(rho), _ptr(nvalid), _ptr(ws), ws.numel(),
+                                     _stream(x.device)))
+    return torch.view_as_complex(rho), int(nvalid.item())
+
+
+def rdm_ll_sums(apply, x: torch.Tensor, r_prime: torch.Tensor, n_up: int, flux: int, levels: int,
+                by_spin: bool = False, chunk_points: int = 4):
+    """rdm_accumulate's (rho, nvalid) with the log-amplitudes from ``apply`` (complex log psi of
+    [rows, N, 2]): one call on x, then the displaced rows of ``chunk_points`` points at a time, so
+    at most chunk_points B N rows are in flight."""
+    x, r_prime = _check_cuda(x), _check_cuda(r_prime)
+    B, N, _ = x.shape
+    logpsi = _log_pairs(apply(x))
+    parts = []
+    for p0 in range(0, r_prime.shape[0], chunk_points):
+        xp = rdm_displace(x, r_prime[p0:p0 + chunk_points])
+        parts.append(_log_pairs(apply(xp.reshape(-1, N, 2))))
+    return rdm_accumulate(x, r_prime, logpsi, torch.cat(parts), n_up, flux, levels, by_spin)

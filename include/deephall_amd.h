@@ -436,6 +436,44 @@ int dh_swap_reduce(const float* logpsi, const float* logpsi_s, int B, int nelec,
                    const int32_t* pair, const int32_t* sector, const int32_t* start, double* sums, void* stream);
 size_t dh_swap_workspace_bytes(int B, int A);
 
+/* ---- Landau-level-resolved one-body density matrix -----------------------------------------
+ * Basis: the monopole harmonics Y_{Q,Q+n,m}, Q = flux / 2, of the Landau levels n = 0..levels-1,
+ * m = -(Q + n)..(Q + n); level-major, m ascending inside a level:
+ * norb = dh_rdm_norb(flux, levels) = levels (flux + 1) + levels (levels - 1).  The general-l
+ * formula of one_rdm.py:31-51 (the reference calls it with l = Q only), cos theta clipped to
+ * +-(1 - 1e-4) as there; double arithmetic.  The per-orbital constants are computed on the host,
+ * once per (device, flux, levels), and stay in a device table for the life of the process.
+ *
+ * dh_monopole_harmonics  out[n][norb] complex float32 (re, im) at n points (theta, phi): the
+ *                        format of dh_monopole_orbitals, whose flux + 1 values are the level-0 block.
+ * dh_rdm_displace        xp[P][B][nelec][nelec][2]: row (p B + b) nelec + a is walker b of
+ *                        x[B][nelec][2] with electron a moved to r_prime[p][b] (r_prime[P][B][2]).
+ * dh_rdm_accumulate      OVERWRITES rho[S][norb][norb][2] (re, im; double; S = 2, up then down,
+ *                        when by_spin, else 1) with the SUM over the kept samples (b, p) of
+ *                          4 pi u_i conj(v_j),  v_j = Y_j(r_prime[p][b]),
+ *                          u_i = sum_a exp(logpsi_p[(p B + b) nelec + a] - logpsi[b]) Y_i(x[b][a]),
+ *                        the sum over a restricted to the slots below n_up (up) or from n_up on
+ *                        (down) when by_spin.  logpsi[B][2] and logpsi_p[P B nelec][2] are float32
+ *                        (re, im) as dh_logpsi writes them for x and for xp; the difference is
+ *                        exponentiated in double.  A sample is dropped when any of its nelec + 1
+ *                        log-amplitudes or any of its ratios is not finite; nvalid (one device
+ *                        int32) = the number kept, so rho / nvalid is the estimate.  The samples
+ *                        are reduced on the device in a fixed order without float atomics: two
+ *                        calls on the same inputs give identical bits.  workspace:
+ *                        dh_rdm_workspace_bytes(B, nelec, flux, levels, P) device bytes (sized for
+ *                        S = 2).
+ * Checked before any device call, DH_EINVAL otherwise (the two queries then return 0):
+ * 1 <= levels <= DH_RDM_MAX_LEVELS, 0 <= flux <= 126, 1 <= nelec <= 32, 0 <= n_up <= nelec,
+ * B >= 1, P >= 1, P B <= 2^30, P B nelec^2 < 2^31, non-null pointers, the workspace size. */
+#define DH_RDM_MAX_LEVELS 4
+int dh_rdm_norb(int flux, int levels);
+size_t dh_rdm_workspace_bytes(int B, int nelec, int flux, int levels, int P);
+int dh_monopole_harmonics(const float* points, int n, int flux, int levels, float* out, void* stream);
+int dh_rdm_displace(const float* x, const float* r_prime, int B, int nelec, int P, float* xp, void* stream);
+int dh_rdm_accumulate(const float* x, const float* r_prime, const float* logpsi, const float* logpsi_p, int B,
+                      int nelec, int n_up, int flux, int levels, int P, int by_spin, double* rho, int32_t* nvalid,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- log psi supplied by the caller: the arbitrary-callable boundary ---------------------
  * The reference's make_mcmc_step(batch_network, ...) (mcmc.py:105-150) and
  * make_local_kinetic_energy(f, Q, r) (hamiltonian.py:83-172) accept ANY log psi.  For one
