@@ -104,6 +104,11 @@ EXPORTS = [
     "dh_monopole_harmonics",
     "dh_rdm_displace",
     "dh_rdm_accumulate",
+    "dh_create_halperin",
+    "dh_spin_workspace_bytes",
+    "dh_spin_exchange",
+    "dh_spin_ratios",
+    "dh_spin_reduce",
 ]
 
 DH_SWAP_MAX_ANGLES = 64
@@ -283,6 +288,16 @@ def load(path: Path | str | None = None):
     lib.dh_rdm_displace.restype = i32
     lib.dh_rdm_accumulate.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]
     lib.dh_rdm_accumulate.restype = i32
+    lib.dh_create_halperin.argtypes = [C.POINTER(DhConfig), i32, i32, i32, C.POINTER(vp)]
+    lib.dh_create_halperin.restype = i32
+    lib.dh_spin_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.dh_spin_workspace_bytes.restype = sz
+    lib.dh_spin_exchange.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    lib.dh_spin_exchange.restype = i32
+    lib.dh_spin_ratios.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]
+    lib.dh_spin_ratios.restype = i32
+    lib.dh_spin_reduce.argtypes = [vp, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp]
+    lib.dh_spin_reduce.restype = i32
     lib.dh_grad_cotangent.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.dh_grad_cotangent.restype = i32
     lib.dh_adam_update.argtypes = [vp, vp, vp, vp, sz, f32, f32, f32, f32, i32, vp]

@@ -44,6 +44,7 @@ class NetworkType(str, enum.Enum):
     laughlin = "laughlin"
     jain = "jain"
     pfaffian = "pfaffian"
+    halperin = "halperin"
 
 
 class OrbitalType(str, enum.Enum):
@@ -95,12 +96,25 @@ class PfaffianNetwork:
 
 
 @dataclass
+class HalperinNetwork:
+    """Halperin (m_up, m_dn, n) two-component state (not in the reference; networks/halperin.py).
+    ``exponents``: (m_up, m_dn, n), the intra-species exponents odd, n >= 0; the system's flux must
+    be m_up (n_up - 1) + n n_dn and m_dn (n_dn - 1) + n n_up.  The default is the singlet at 2/5."""
+
+    exponents: tuple = (3, 3, 2)
+
+    def __post_init__(self):
+        self.exponents = tuple(int(e) for e in self.exponents)  # a list from a config file
+
+
+@dataclass
 class Network:
     type: NetworkType = NetworkType.psiformer
     orbital: OrbitalType = OrbitalType.full
     psiformer: PsiformerNetwork = field(default_factory=PsiformerNetwork)
     jain: JainNetwork = field(default_factory=JainNetwork)
     pfaffian: PfaffianNetwork = field(default_factory=PfaffianNetwork)
+    halperin: HalperinNetwork = field(default_factory=HalperinNetwork)
 
 
 @dataclass
@@ -160,9 +174,10 @@ class OptimizerMinsr:
 @dataclass
 class Pretrain:
     """Fidelity pretraining onto a trial state before the energy minimisation (pretrain.py; not
-    in the reference).  ``iterations``: 0 switches it off.  ``reference``: "laughlin", "jain" or
-    "pfaffian", built for the run's system as the overlap estimator builds it (``network.jain`` /
-    ``network.pfaffian`` choose p and the occupation).  ``lr``: None is the chosen optimizer's own
+    in the reference).  ``iterations``: 0 switches it off.  ``reference``: "laughlin", "jain",
+    "pfaffian" or "halperin", built for the run's system as the overlap estimator builds it
+    (``network.jain`` / ``network.pfaffian`` choose p and the occupation, ``network.halperin`` the
+    exponents).  ``lr``: None is the chosen optimizer's own
     schedule; either way it starts at t = 0 and the training after it starts at t = 0 again."""
 
     iterations: int = 0

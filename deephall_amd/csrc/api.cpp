@@ -229,7 +229,44 @@ int create_pfaffian(const dh_config* cfg, dh_handle** out) {
   *out = analytic_handle(cfg, dh_handle::PFAFFIAN, {});
   return DH_OK;
 }
+
+// Halperin (m_up, m_dn, n) (halperin.hip): both species at the flux of their degree in (u, v);
+// the exponent of an empty or single-electron species is free beyond its parity
+int create_halperin(const dh_config* cfg, int m_up, int m_dn, int n_int, dh_handle** out) {
+  const int N = cfg->n_up + cfg->n_dn;
+  if (int rc = check_analytic(cfg, "Halperin", 1)) return rc;
+  if (m_up < 1 || m_dn < 1 || m_up % 2 == 0 || m_dn % 2 == 0)
+    return fail(DH_EINVAL, "Halperin: m_up and m_dn must be odd and >= 1, got " + std::to_string(m_up) + ", " +
+                               std::to_string(m_dn));
+  if (n_int < 0) return fail(DH_EINVAL, "Halperin: need n >= 0, got " + std::to_string(n_int));
+  const int64_t f_up = (int64_t)m_up * (cfg->n_up - 1) + (int64_t)n_int * cfg->n_dn;
+  const int64_t f_dn = (int64_t)m_dn * (cfg->n_dn - 1) + (int64_t)n_int * cfg->n_up;
+  if (cfg->n_up > 0 && cfg->flux != f_up)
+    return fail(DH_EINVAL, "Halperin: the up electrons live at flux m_up (n_up - 1) + n n_dn = " + std::to_string(f_up) +
+                               ", got " + std::to_string(cfg->flux));
+  if (cfg->n_dn > 0 && cfg->flux != f_dn)
+    return fail(DH_EINVAL, "Halperin: the down electrons live at flux m_dn (n_dn - 1) + n n_up = " +
+                               std::to_string(f_dn) + ", got " + std::to_string(cfg->flux));
+  if (halperin_smem_bytes(N, true) > 160 * 1024)
+    return fail(DH_EINVAL, "Halperin: N = " + std::to_string(N) + " needs " + std::to_string(halperin_smem_bytes(N, true)) +
+                               " bytes of LDS; the one-workgroup kernel has 160 KiB");
+  dh_handle* h = analytic_handle(cfg, dh_handle::HALPERIN, {});
+  h->halperin[0] = m_up;
+  h->halperin[1] = m_dn;
+  h->halperin[2] = n_int;
+  *out = h;
+  return DH_OK;
+}
 }  // namespace
+
+int dh_create_halperin(const dh_config* cfg, int m_up, int m_dn, int n_inter, dh_handle** out) {
+  if (!cfg || !out) return fail(DH_EINVAL, "Halperin: null argument");
+  if (cfg->struct_size != sizeof(dh_config))
+    return fail(DH_EINVAL, "Halperin: dh_config.struct_size must equal sizeof(dh_config)");
+  if (cfg->network_type != DH_NETWORK_HALPERIN)
+    return fail(DH_EINVAL, "Halperin: dh_create_halperin needs network_type DH_NETWORK_HALPERIN");
+  return create_halperin(cfg, m_up, m_dn, n_inter, out);
+}
 
 int dh_create_cf(const dh_config* cfg, const int* occ, int n_occ, dh_handle** out) {
   if (!cfg || !out || !occ) return fail(DH_EINVAL, "null argument");
@@ -252,6 +289,8 @@ int dh_create(const dh_config* cfg, dh_handle** out) {
   }
   if (cfg->network_type == DH_NETWORK_JAIN) return create_jain(cfg, nullptr, 0, out);
   if (cfg->network_type == DH_NETWORK_PFAFFIAN) return create_pfaffian(cfg, out);
+  if (cfg->network_type == DH_NETWORK_HALPERIN)
+    return fail(DH_EINVAL, "Halperin: the exponents (m_up, m_dn, n) are arguments of dh_create_halperin, not dh_create");
   if (cfg->network_type != DH_NETWORK_PSIFORMER) return fail(DH_EINVAL, "bad network type");
   const int N = cfg->n_up + cfg->n_dn;
   if (cfg->n_up < 0 || cfg->n_dn < 0 || N < 1 || N > 32) return fail(DH_EINVAL, "need 1 <= N <= 32 electrons");
@@ -831,7 +870,9 @@ int launch_trial(dh_handle* h, const float* x, float* logpsi, float* e_l, float*
     HIP_TRY(hipMemcpy(h->expo, h->expo_host.data(), h->expo_host.size() * sizeof(int), hipMemcpyHostToDevice));
   }
   PROF(e_l ? PK_DET_ENERGY : PK_DET_VALUE, 0.0, e_l ? 48.0 * nw : 8.0 * nw * h->d.N);
-  if (h->state == dh_handle::PFAFFIAN)
+  if (h->state == dh_handle::HALPERIN)
+    launch_halperin(h->d, x, h->halperin[0], h->halperin[1], h->halperin[2], logpsi, e_l, obs, nw, s);
+  else if (h->state == dh_handle::PFAFFIAN)
     launch_pfaffian(h->d, x, h->cfg.cf_flux, logpsi, e_l, obs, nw, s);
   else if (h->state == dh_handle::JAIN)
     launch_cf(h->d, x, h->expo, h->cf_dense, logpsi, e_l, obs, nw, s);
@@ -1309,6 +1350,58 @@ int dh_rdm_accumulate(const float* x, const float* r_prime, const float* logpsi,
   HIP_TRY(rdm_table(flux, levels, &table));
   HIP_TRY(launch_rdm_accumulate(x, r_prime, logpsi, logpsi_p, B, nelec, n_up, flux, levels, P, by_spin != 0, table,
                                 rho, nvalid, workspace, (hipStream_t)stream));
+  return check_launch();
+}
+
+// ---- total-spin estimator (spin.hip): no handle either ----
+
+namespace {
+const char* spin_size_error(int B, int n_up, int n_dn) {
+  if (B < 1) return "spin: B < 1";
+  if (n_up < 0 || n_dn < 0 || n_up + n_dn < 1 || n_up + n_dn > 32) return "spin: n_up, n_dn < 0 or n_up + n_dn outside 1..32";
+  if ((int64_t)B * n_up * n_dn > INT32_MAX) return "spin: B n_up n_dn >= 2^31";
+  return nullptr;
+}
+const char* spin_window_error(int n_up, int n_dn, int pair0, int pair1) {
+  if (pair0 < 0 || pair1 <= pair0 || pair1 > n_up * n_dn) return "spin: need 0 <= pair0 < pair1 <= n_up n_dn";
+  return nullptr;
+}
+}  // namespace
+
+size_t dh_spin_workspace_bytes(int B, int n_up, int n_dn) {
+  if (spin_size_error(B, n_up, n_dn)) return 0;
+  return align64(spin_workspace_bytes(B, n_up * n_dn));
+}
+
+int dh_spin_exchange(const float* x, int B, int nelec, int n_up, int n_dn, int pair0, int pair1, float* xs,
+                     void* stream) {
+  if (!x || !xs) return fail(DH_EINVAL, "spin: null pointer");
+  if (const char* e = spin_size_error(B, n_up, n_dn)) return fail(DH_EINVAL, e);
+  if (n_up + n_dn != nelec) return fail(DH_EINVAL, "spin: n_up + n_dn != nelec");
+  if (const char* e = spin_window_error(n_up, n_dn, pair0, pair1)) return fail(DH_EINVAL, e);
+  launch_spin_exchange(x, B, nelec, n_up, n_dn, pair0, pair1, xs, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_spin_ratios(const float* logpsi, const float* logpsi_s, int B, int n_up, int n_dn, int pair0, int pair1,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (!logpsi || !logpsi_s || !workspace) return fail(DH_EINVAL, "spin: null pointer");
+  if (const char* e = spin_size_error(B, n_up, n_dn)) return fail(DH_EINVAL, e);
+  if (const char* e = spin_window_error(n_up, n_dn, pair0, pair1)) return fail(DH_EINVAL, e);
+  if (workspace_bytes < dh_spin_workspace_bytes(B, n_up, n_dn))
+    return fail(DH_ENOMEM, "spin: workspace smaller than dh_spin_workspace_bytes");
+  launch_spin_ratios(logpsi, logpsi_s, B, pair0, pair1, workspace, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_spin_reduce(const float* logpsi, int B, int n_up, int n_dn, void* workspace, size_t workspace_bytes,
+                   double* s2, double* pairs, double* total, int32_t* nvalid, void* stream) {
+  if (!logpsi || !workspace || !s2 || !total || !nvalid) return fail(DH_EINVAL, "spin: null pointer");
+  if (const char* e = spin_size_error(B, n_up, n_dn)) return fail(DH_EINVAL, e);
+  if (n_up * n_dn > 0 && !pairs) return fail(DH_EINVAL, "spin: null pointer");
+  if (workspace_bytes < dh_spin_workspace_bytes(B, n_up, n_dn))
+    return fail(DH_ENOMEM, "spin: workspace smaller than dh_spin_workspace_bytes");
+  launch_spin_reduce(logpsi, B, n_up, n_dn, workspace, s2, pairs, total, nvalid, (hipStream_t)stream);
   return check_launch();
 }
 

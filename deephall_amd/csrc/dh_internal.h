@@ -373,6 +373,18 @@ void launch_rdm_displace(const float* x, const float* r_prime, int B, int N, int
 hipError_t launch_rdm_accumulate(const float* x, const float* r_prime, const float* logpsi, const float* logpsi_p,
                                  int B, int N, int n_up, int flux, int levels, int P, int by_spin,
                                  const double* table, double* rho, int32_t* nvalid, void* workspace, hipStream_t s);
+// Total-spin estimator (spin.hip): the exchanged rows of the pairs [pair0, pair1) (pair
+// p = i n_dn + (j - n_up) of an up slot i and a down slot j), their ratios psi(R_p) / psi(R) into
+// the workspace, and, once every pair is there, S^2_loc per walker with the sums over the valid
+// walkers.  The limits (nelec <= 32, B n_up n_dn < 2^31, 0 <= pair0 < pair1 <= n_up n_dn for the
+// first two) are the callers' to check: then no grid is empty.
+size_t spin_workspace_bytes(int B, int P);
+void launch_spin_exchange(const float* x, int B, int N, int n_up, int n_dn, int pair0, int pair1, float* xs,
+                          hipStream_t s);
+void launch_spin_ratios(const float* logpsi, const float* logpsi_s, int B, int pair0, int pair1, void* workspace,
+                        hipStream_t s);
+void launch_spin_reduce(const float* logpsi, int B, int n_up, int n_dn, void* workspace, double* s2, double* pairs,
+                        double* total, int32_t* nvalid, hipStream_t s);
 bool det_precontract(const Dims& d);
 void launch_det_energy(const Dims& d, const float* F, const float* x, const float* geo, const float* jastrow,
                        const float* norm, float* e_l, float* obs, int nw, hipStream_t s, float* phic);
@@ -480,6 +492,14 @@ void launch_cf(const Dims& d, const float* x, const int* tab, int n_dense, float
 size_t pfaffian_smem_bytes(int N, bool energy);
 void launch_pfaffian(const Dims& d, const float* x, int p, float* logpsi, float* e_l, float* obs, int nw,
                      hipStream_t s);
+
+// halperin.hip: the same two launches for a Halperin (m_up, m_dn, n) state: the slots below
+// d.n_up up, the rest down, no table.  The value launch packs 256 / halperin_group(N) walkers into
+// a workgroup; LDS per workgroup by instantiation.
+int halperin_group(int N);
+size_t halperin_smem_bytes(int N, bool energy);
+void launch_halperin(const Dims& d, const float* x, int m_up, int m_dn, int n_int, float* logpsi, float* e_l,
+                     float* obs, int nw, hipStream_t s);
 
 // det.hip: backward of log psi = J + log sum_k det Phi_k for per-walker cotangents ct[nw][2]:
 // dF [nw*N][ld_orb] (all columns written) and jg[nw][2] = ct.re * dJ / d(ee_par, ee_anti)

@@ -16,6 +16,9 @@ with the same names, options, value/state keys and digests:
   reference): the basis Y_{Q,Q+n,m} of the first few levels, the displaced rows and the reduction
   over walkers and r' points in double are csrc/rdm.hip (``dh_monopole_harmonics``, ``dh_rdm_*``);
   its digest gives the occupation of each level and the weight above the last one kept;
+* the total spin <S^2> (observables/spin_square.py, not in the reference) exchanges one up and one
+  down electron: the exchanged rows, the ratios and the reduction over walkers in double are
+  csrc/spin.hip (``dh_spin_*``); S (S + 1) on every walker of a total-spin eigenstate;
 * every wavefunction value goes through ``dh_logpsi`` (Psiformer or the native Laughlin
   state), the walk through ``dh_mcmc_step``;
 * ``evaluate`` is a minimal stand-in for NetObs's own evaluation loop (restore, burn-in,
@@ -27,7 +30,7 @@ with the same names, options, value/state keys and digests:
 from .adaptor import DeepHallAdaptor, DeepHallAuxData
 from .estimator import Estimator, Observable, evaluate
 from .hall_system import HallSystem
-from .observables import density, ll_rdm, one_rdm, overlap, pair_corr, renyi2
+from .observables import density, ll_rdm, one_rdm, overlap, pair_corr, renyi2, spin_square
 
 
 class _Registry(dict):
@@ -55,6 +58,7 @@ EXTRA_ESTIMATORS = _Registry({
     "renyi2": renyi2.DEFAULT,
 }, more={
     "ll_rdm": ll_rdm.DEFAULT,
+    "spin_square": spin_square.DEFAULT,
 })
 
 # The own keys are the reference's ``deephall@`` names, so the registry still lists exactly what

@@ -111,6 +111,75 @@ def swap_purity(apply, x: torch.Tensor, thetas, nspins):
     return swap_reduce(logpsi, logpsi_s, nspins, M, pair, sector, start), counts.long()
 
 
+# ---- total spin by up-down exchange (csrc/spin.hip) -----------------------------------------------
+
+def spin_exchange(x: torch.Tensor, nspins, pair0: int = 0, pair1: int | None = None) -> torch.Tensor:
+    """xs[pair1 - pair0, B, N, 2]: xs[p - pair0, b] is walker b of x[B, N, 2] with the slots of pair
+    p = i n_dn + (j - n_up) (an up slot i, a down slot j) exchanged.  pair1 None: all n_up n_dn pairs."""
+    x = _check_cuda(x)
+    B, N, _ = x.shape
+    n_up, n_dn = int(nspins[0]), int(nspins[1])
+    pair1 = n_up * n_dn if pair1 is None else int(pair1)
+    xs = torch.empty(max(pair1 - int(pair0), 0), B, N, 2, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().dh_spin_exchange(_ptr(x), B, N, n_up, n_dn, int(pair0), pair1, _ptr(xs), _stream(x.device)))
+    return xs
+
+
+def spin_workspace(B: int, nspins, device) -> torch.Tensor:
+    """The buffer dh_spin_ratios fills and dh_spin_reduce reads (float64: 16-byte aligned)."""
+    n_up, n_dn = int(nspins[0]), int(nspins[1])
+    nbytes = int(_lib.load().dh_spin_workspace_bytes(int(B), n_up, n_dn))
+    if nbytes < 1:
+        raise ValueError(f"spin_square: B = {B}, nspins = {tuple(nspins)} outside B >= 1, 1 <= N <= 32, B n_up n_dn < 2^31")
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def spin_ratios(logpsi: torch.Tensor, logpsi_s: torch.Tensor, nspins, pair0: int, pair1: int, ws: torch.Tensor):
+    """Store exp(logpsi_s - logpsi) of the pairs [pair0, pair1) in ws; logpsi [B, 2] and logpsi_s
+    [(pair1 - pair0) B, 2] float32 (dh_logpsi's layout; rows as spin_exchange orders them)."""
+    logpsi, logpsi_s = _check_cuda(logpsi), _check_cuda(logpsi_s)
+    B = logpsi.shape[0]
+    if logpsi.shape != (B, 2) or logpsi_s.shape != ((int(pair1) - int(pair0)) * B, 2):
+        raise ValueError(f"spin_ratios: shapes {tuple(logpsi.shape)}, {tuple(logpsi_s.shape)} do not fit the "
+                         f"pairs {pair0}..{pair1}")
+    _lib.check(_lib.load().dh_spin_ratios(_ptr(logpsi), _ptr(logpsi_s), B, int(nspins[0]), int(nspins[1]), int(pair0),
+                                          int(pair1), _ptr(ws), ws.numel() * 8, _stream(logpsi.device)))
+
+
+def spin_reduce(logpsi: torch.Tensor, nspins, ws: torch.Tensor):
+    """(s2[B] complex128, S^2_loc per walker and NaN for an invalid one; pairs[n_up, n_dn]
+    complex128, the valid walkers' sums of each pair's ratio; total, their sum of s2; nvalid) once
+    every pair is in ws.  nvalid is read back from the device (one synchronisation)."""
+    logpsi = _check_cuda(logpsi)
+    B = logpsi.shape[0]
+    n_up, n_dn = int(nspins[0]), int(nspins[1])
+    dev = logpsi.device
+    s2 = torch.empty(B, 2, dtype=torch.float64, device=dev)
+    pairs = torch.zeros(n_up, n_dn, 2, dtype=torch.float64, device=dev)
+    total = torch.empty(2, dtype=torch.float64, device=dev)
+    nvalid = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().dh_spin_reduce(_ptr(logpsi), B, n_up, n_dn, _ptr(ws), ws.numel() * 8, _ptr(s2),
+                                          _ptr(pairs) if n_up * n_dn else None, _ptr(total), _ptr(nvalid), _stream(dev)))
+    return torch.view_as_complex(s2), torch.view_as_complex(pairs), torch.view_as_complex(total), int(nvalid.item())
+
+
+def spin_square_sums(apply, x: torch.Tensor, nspins, max_rows: int | None = None):
+    """spin_reduce's results with the log-amplitudes from ``apply`` (complex log psi of
+    [rows, N, 2]): one call on x, then the exchanged rows of whole pairs, at most ``max_rows``
+    rows (and at least one pair) per call; None: all n_up n_dn pairs in one call."""
+    x = _check_cuda(x)
+    B, N, _ = x.shape
+    P = int(nspins[0]) * int(nspins[1])
+    ws = spin_workspace(B, nspins, x.device)
+    logpsi = _log_pairs(apply(x))
+    step = P if max_rows is None else max(1, int(max_rows) // B)
+    for p0 in range(0, P, max(step, 1)):
+        p1 = min(p0 + step, P)
+        xs = spin_exchange(x, nspins, p0, p1)
+        spin_ratios(logpsi, _log_pairs(apply(xs.reshape(-1, N, 2))), nspins, p0, p1, ws)
+    return spin_reduce(logpsi, nspins, ws)
+
+
 # ---- Landau-level-resolved one-body density matrix (csrc/rdm.hip) --------------------------------
 
 def rdm_norb(flux: int, levels: int) -> int:

@@ -3,6 +3,7 @@
 from __future__ import annotations
 
 from ..config import Network, NetworkType, System
+from .halperin import Halperin, HalperinCallable
 from .jain import Jain, JainCallable
 from .laughlin import Laughlin, LaughlinQuasiparticle
 from .pfaffian import MooreRead, MooreReadCallable
@@ -20,6 +21,8 @@ def make_network(system: System, network: Network) -> Psiformer:
                     occupation=network.jain.occupation, system=system)
     if ntype == NetworkType.pfaffian.value:  # pfaffian.hip: Moore-Read at flux 2p(N-1)-1
         return MooreRead(flux=system.flux, nspins=system.nspins, cf_flux=network.pfaffian.cf_flux, system=system)
+    if ntype == NetworkType.halperin.value:  # halperin.hip: (m_up, m_dn, n) on the two species of nspins
+        return Halperin(flux=system.flux, nspins=system.nspins, exponents=network.halperin.exponents, system=system)
     if ntype == NetworkType.psiformer.value:
         return Psiformer(
             Q=Q,
@@ -35,4 +38,4 @@ def make_network(system: System, network: Network) -> Psiformer:
 
 
 __all__ = ["make_network", "Psiformer", "Laughlin", "LaughlinQuasiparticle", "Jain", "JainCallable",
-           "MooreRead", "MooreReadCallable"]
+           "MooreRead", "MooreReadCallable", "Halperin", "HalperinCallable"]

@@ -25,7 +25,7 @@ from .psiformer import NetworkSpec, ParamTree, Psiformer, _ptr, _stream, get_han
 
 
 def analytic_spec(system, **fields) -> NetworkSpec:
-    """The NetworkSpec of a parameter-free trial state (Laughlin, Jain, MooreRead): no network
+    """The NetworkSpec of a parameter-free trial state (Laughlin, Jain, MooreRead, Halperin): no network
     dimensions, the sphere and the interaction from ``system``, the state's own fields as keywords."""
     radius = getattr(system, "radius", None) if system is not None else None
     lam = getattr(system, "interaction_strength", 1.0) if system is not None else 1.0

@@ -59,6 +59,7 @@ class NetworkSpec:
     excitation_lz: float = 0.0
     cf_flux: int = 1
     occupation: tuple | None = None  # jain: ((Lambda level, 2 m), ...) ints; None: the filled-levels ground state
+    halperin: tuple | None = None  # halperin: (m_up, m_dn, n) ints, the arguments of dh_create_halperin
 
     @property
     def nelec(self) -> int:
@@ -82,7 +83,8 @@ class NetworkSpec:
         c.num_heads, c.heads_dim, c.num_layers = self.num_heads, self.heads_dim, self.num_layers
         c.ndets = self.ndets
         c.orbital_type = {"full": 0, "sparse": 1}.get(str(getattr(self.orbital_type, "value", self.orbital_type)), -1)
-        c.network_type = {"psiformer": 0, "laughlin": 1, "jain": 2, "pfaffian": 3}.get(str(getattr(self.network_type, "value", self.network_type)), -1)
+        c.network_type = {"psiformer": 0, "laughlin": 1, "jain": 2, "pfaffian": 3, "halperin": 4}.get(
+            str(getattr(self.network_type, "value", self.network_type)), -1)
         c.excitation_lz = float(self.excitation_lz)
         c.cf_flux = int(self.cf_flux)
         return c
@@ -100,6 +102,8 @@ class NativeHandle:
         if spec.occupation is not None:
             occ = (C.c_int * (2 * len(spec.occupation)))(*[int(v) for pair in spec.occupation for v in pair])
             _lib.check(self.lib.dh_create_cf(C.byref(cfg), occ, len(spec.occupation), C.byref(self.h)))
+        elif spec.halperin is not None:
+            _lib.check(self.lib.dh_create_halperin(C.byref(cfg), *(int(e) for e in spec.halperin), C.byref(self.h)))
         else:
             _lib.check(self.lib.dh_create(C.byref(cfg), C.byref(self.h)))
         nseg = self.lib.dh_ref_layout(self.h, None, 0)
@@ -193,8 +197,8 @@ def flatten_params(params) -> dict:
 
 def param_shapes(spec: NetworkSpec) -> dict:
     """Shapes of the reference's parameter tree (Flax auto-naming)."""
-    if spec.network_type in ("laughlin", "jain", "pfaffian"):
-        return {}  # laughlin.py has no parameters; neither have the Jain and Moore-Read states
+    if spec.network_type in ("laughlin", "jain", "pfaffian", "halperin"):
+        return {}  # laughlin.py has no parameters; neither have the Jain, Moore-Read and Halperin states
     D, H, dh = spec.D, spec.num_heads, spec.heads_dim
     M, N, K = spec.M, spec.nelec, spec.ndets
     p = "PsiformerLayers_0/"

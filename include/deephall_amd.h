@@ -58,6 +58,8 @@ extern "C" {
                             filled-levels ground state N = 4 Q1 + 4, dh_create_cf any occupation */
 #define DH_NETWORK_PFAFFIAN 3 /* Moore-Read Pfaffian state (no parameters): N even, p = cf_flux >= 1 and
                                 flux = 2 p (N - 1) - 1 exactly (nu = 1/2 at p = 1); N <= 28 by the kernel's LDS */
+#define DH_NETWORK_HALPERIN 4 /* Halperin (m_up, m_dn, n) two-component state (no parameters): dh_create_halperin
+                                only; dh_create refuses the type, the exponents are not dh_config fields */
 #define DH_ORBITAL_FULL 0
 #define DH_ORBITAL_SPARSE 1 /* blocks.py:52-62: 8 features per (j, k) mixed into the M harmonics by
                                lll_weight; folded into the full layout when parameters are set */
@@ -94,6 +96,15 @@ int dh_create(const dh_config* cfg, dh_handle** out);
  * no orbital twice.  The handle has no parameters and serves dh_logpsi, dh_mcmc_step,
  * dh_local_energy, dh_potential and dh_energy_stats as a Laughlin handle does. */
 int dh_create_cf(const dh_config* cfg, const int* occ, int n_occ, dh_handle** out);
+/* Halperin state (cfg->network_type = DH_NETWORK_HALPERIN): with w_ik = u_i v_k - u_k v_i and the
+ * slots below n_up up, the rest down,
+ *   log psi = sum_{i<k} c_ik log w_ik,  c_ik = m_up (both up), m_dn (both down), n_inter (one of each),
+ * no determinant, no normalisation, Im log psi the principal phase.  m_up and m_dn odd and >= 1,
+ * n_inter >= 0, 1 <= N <= 32, 1 <= flux <= 126, flux = m_up (n_up - 1) + n_inter n_dn if n_up > 0
+ * and flux = m_dn (n_dn - 1) + n_inter n_up if n_dn > 0 (the exponent of an empty or single-electron
+ * species is bound by its parity only); anything else is DH_EINVAL with a message that starts
+ * "Halperin".  The handle has no parameters and serves the calls a dh_create_cf handle serves. */
+int dh_create_halperin(const dh_config* cfg, int m_up, int m_dn, int n_inter, dh_handle** out);
 void dh_destroy(dh_handle* h);
 const char* dh_last_error(void);
 const char* dh_version(void);
@@ -473,6 +484,38 @@ int dh_rdm_displace(const float* x, const float* r_prime, int B, int nelec, int 
 int dh_rdm_accumulate(const float* x, const float* r_prime, const float* logpsi, const float* logpsi_p, int B,
                       int nelec, int n_up, int flux, int levels, int P, int by_spin, double* rho, int32_t* nvalid,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Total spin: <S^2> by exchanging one up and one down electron ----------------------------
+ * Walkers x[B][nelec][2]; the slots below n_up are up electrons (n_up + n_dn = nelec).  Pair
+ * p = i n_dn + (j - n_up) of an up slot i and a down slot j, P = n_up n_dn pairs; R_p is the walker
+ * with the coordinates of slots i and j exchanged (copies of the stored floats), and
+ *   S^2_loc(R) = ((n_up - n_dn) / 2)^2 + nelec / 2 - sum_p psi(R_p) / psi(R).
+ *
+ * dh_spin_exchange  xs[(pair1 - pair0) B][nelec][2]: row (p - pair0) B + b is R_p of walker b, for
+ *                   the pairs pair0 <= p < pair1 (0 <= pair0 < pair1 <= P).
+ * dh_spin_ratios    stores exp(logpsi_s[(p - pair0) B + b] - logpsi[b]) of that window in the
+ *                   workspace, in double from the float32 logs (re, im as dh_logpsi writes them for
+ *                   x and xs); NaN where a log or the ratio is not finite.  What a pair stores does
+ *                   not depend on the window it came in.
+ * dh_spin_reduce    after EVERY pair has been stored: s2[B][2] (re, im; double) = S^2_loc per
+ *                   walker, the pairs added in ascending p; pairs[n_up][n_dn][2], the sum of the
+ *                   ratio of each pair over the valid walkers; total[2], the sum of s2 over them;
+ *                   nvalid (one device int32), their number.  A walker is valid when its own log
+ *                   and all its P ratios are finite; an invalid one gets s2 = NaN and enters no sum.
+ *                   Double arithmetic, a fixed order, no float atomics: two calls give identical
+ *                   bits, and so do one window of all pairs and one window per pair.  With P = 0
+ *                   (no exchange, no ratios, pairs may be null) s2 = (nelec / 2)(nelec / 2 + 1).
+ * workspace: dh_spin_workspace_bytes(B, n_up, n_dn) device bytes, 16-byte aligned, the same buffer
+ * for the ratios and the reduce.  Checked before any device call, DH_EINVAL otherwise (the query
+ * then returns 0): B >= 1, n_up, n_dn >= 0, 1 <= n_up + n_dn <= 32, B n_up n_dn < 2^31, the window,
+ * non-null pointers; a short workspace is DH_ENOMEM.  No dh_handle, as for the swap kernels. */
+size_t dh_spin_workspace_bytes(int B, int n_up, int n_dn);
+int dh_spin_exchange(const float* x, int B, int nelec, int n_up, int n_dn, int pair0, int pair1, float* xs,
+                     void* stream);
+int dh_spin_ratios(const float* logpsi, const float* logpsi_s, int B, int n_up, int n_dn, int pair0, int pair1,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int dh_spin_reduce(const float* logpsi, int B, int n_up, int n_dn, void* workspace, size_t workspace_bytes,
+                   double* s2, double* pairs, double* total, int32_t* nvalid, void* stream);
 
 /* ---- log psi supplied by the caller: the arbitrary-callable boundary ---------------------
  * The reference's make_mcmc_step(batch_network, ...) (mcmc.py:105-150) and
