@@ -24,7 +24,9 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I", st
 # between MFMAs costs more issue cycles than it saves, MI355X_MICROARCH.md cycle table); the
 # fused channel tail likewise (round 5: the packed form of layer 1's residual spilled 44 B per
 # lane; without it no spills, channel launches 440 -> 438 us, profiles/r05_v26_lnch_noslp_ab.txt)
-EXTRA = {"gemm_x6.hip": ["-fno-slp-vectorize"], "gemm_lnch.hip": ["-fno-slp-vectorize"]}
+# sfactor.hip: no contraction, so its walker functions round alike in every kernel they are inlined into
+EXTRA = {"gemm_x6.hip": ["-fno-slp-vectorize"], "gemm_lnch.hip": ["-fno-slp-vectorize"],
+         "sfactor.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -109,10 +109,16 @@ EXPORTS = [
     "dh_spin_exchange",
     "dh_spin_ratios",
     "dh_spin_reduce",
+    "dh_sf_nlm",
+    "dh_sf_workspace_bytes",
+    "dh_sf_pairs",
+    "dh_sf_multipoles",
+    "dh_sf_accumulate",
 ]
 
 DH_SWAP_MAX_ANGLES = 64
 DH_RDM_MAX_LEVELS = 4
+DH_SF_MAX_L = 64
 
 DH_NFID = 5  # dh_fidelity_partial: m, S re, S im, S2, n
 
@@ -298,6 +304,16 @@ def load(path: Path | str | None = None):
     lib.dh_spin_ratios.restype = i32
     lib.dh_spin_reduce.argtypes = [vp, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp]
     lib.dh_spin_reduce.restype = i32
+    lib.dh_sf_nlm.argtypes = [i32]
+    lib.dh_sf_nlm.restype = i32
+    lib.dh_sf_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.dh_sf_workspace_bytes.restype = sz
+    lib.dh_sf_pairs.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    lib.dh_sf_pairs.restype = i32
+    lib.dh_sf_multipoles.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    lib.dh_sf_multipoles.restype = i32
+    lib.dh_sf_accumulate.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.dh_sf_accumulate.restype = i32
     lib.dh_grad_cotangent.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.dh_grad_cotangent.restype = i32
     lib.dh_adam_update.argtypes = [vp, vp, vp, vp, sz, f32, f32, f32, f32, i32, vp]

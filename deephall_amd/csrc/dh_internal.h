@@ -385,6 +385,17 @@ void launch_spin_ratios(const float* logpsi, const float* logpsi_s, int B, int p
                         hipStream_t s);
 void launch_spin_reduce(const float* logpsi, int B, int n_up, int n_dn, void* workspace, double* s2, double* pairs,
                         double* total, int32_t* nvalid, hipStream_t s);
+// Static structure factor (sfactor.hip): per-walker pair sums T[B][3][lmax+1] (uu, ud, dd) of
+// P_L(cos gamma_ij) and multipoles rho[B][2][nlm] complex of Y_LM, and their sums over the valid
+// walkers reduced on the device in double.  The limits (nelec <= 32, 0 <= n_up <= nelec,
+// 0 <= lmax <= kSfMaxL, B >= 1, B nelec < 2^31) are the callers' to check: then no grid is empty.
+constexpr int kSfMaxL = 64;
+int sf_nlm(int lmax);
+size_t sf_workspace_bytes(int B, int lmax);
+void launch_sf_pairs(const float* x, int B, int N, int n_up, int lmax, double* T, hipStream_t s);
+void launch_sf_multipoles(const float* x, int B, int N, int n_up, int lmax, double* rho, hipStream_t s);
+void launch_sf_accumulate(const float* x, int B, int N, int n_up, int lmax, bool want, double* pair_sums,
+                          double* rho_sums, int32_t* nvalid, void* workspace, hipStream_t s);
 bool det_precontract(const Dims& d);
 void launch_det_energy(const Dims& d, const float* F, const float* x, const float* geo, const float* jastrow,
                        const float* norm, float* e_l, float* obs, int nw, hipStream_t s, float* phic);

@@ -19,6 +19,10 @@ with the same names, options, value/state keys and digests:
 * the total spin <S^2> (observables/spin_square.py, not in the reference) exchanges one up and one
   down electron: the exchanged rows, the ratios and the reduction over walkers in double are
   csrc/spin.hip (``dh_spin_*``); S (S + 1) on every walker of a total-spin eigenstate;
+* the static structure factor S(L) with its partial, spin, connected and guiding-centre forms
+  (observables/structure_factor.py, not in the reference) needs the walkers only: the Legendre pair
+  sums, the multipoles sum_i Y_LM and their reduction over walkers in double are csrc/sfactor.hip
+  (``dh_sf_*``);
 * every wavefunction value goes through ``dh_logpsi`` (Psiformer or the native Laughlin
   state), the walk through ``dh_mcmc_step``;
 * ``evaluate`` is a minimal stand-in for NetObs's own evaluation loop (restore, burn-in,
@@ -30,7 +34,7 @@ with the same names, options, value/state keys and digests:
 from .adaptor import DeepHallAdaptor, DeepHallAuxData
 from .estimator import Estimator, Observable, evaluate
 from .hall_system import HallSystem
-from .observables import density, ll_rdm, one_rdm, overlap, pair_corr, renyi2, spin_square
+from .observables import density, ll_rdm, one_rdm, overlap, pair_corr, renyi2, spin_square, structure_factor
 
 
 class _Registry(dict):
@@ -59,6 +63,7 @@ EXTRA_ESTIMATORS = _Registry({
 }, more={
     "ll_rdm": ll_rdm.DEFAULT,
     "spin_square": spin_square.DEFAULT,
+    "structure_factor": structure_factor.DEFAULT,
 })
 
 # The own keys are the reference's ``deephall@`` names, so the registry still lists exactly what

@@ -254,3 +254,76 @@ def rdm_ll_sums(apply, x: torch.Tensor, r_prime: torch.Tensor, n_up: int, flux: 
         xp = rdm_displace(x, r_prime[p0:p0 + chunk_points])
         parts.append(_log_pairs(apply(xp.reshape(-1, N, 2))))
     return rdm_accumulate(x, r_prime, logpsi, torch.cat(parts), n_up, flux, levels, by_spin)
+
+
+# ---- static structure factor (csrc/sfactor.hip) ---------------------------------------------------
+
+def sf_nlm(lmax: int) -> int:
+    """Multipoles 0 <= M <= L <= lmax at lm = L (L + 1) / 2 + M: (lmax + 1)(lmax + 2) / 2."""
+    nlm = int(_lib.load().dh_sf_nlm(int(lmax)))
+    if nlm < 1:
+        raise ValueError(f"structure_factor: lmax {lmax} outside 0..{_lib.DH_SF_MAX_L}")
+    return nlm
+
+
+def sf_pairs(x: torch.Tensor, n_up: int, lmax: int) -> torch.Tensor:
+    """T[B, 3, lmax + 1] float64: the sums of P_L(cos gamma_ij) over the pairs i < j of walkers
+    x[B, N, 2] that are both up, up and down, both down.  NaN rows for a walker with a non-finite
+    coordinate."""
+    x = _check_cuda(x)
+    B, N, _ = x.shape
+    T = torch.empty(B, 3, int(lmax) + 1, dtype=torch.float64, device=x.device)
+    _lib.check(_lib.load().dh_sf_pairs(_ptr(x), B, N, int(n_up), int(lmax), _ptr(T), _stream(x.device)))
+    return T
+
+
+def sf_multipoles(x: torch.Tensor, n_up: int, lmax: int) -> torch.Tensor:
+    """rho[B, 2, nlm] complex128: sum_i Y_LM(theta_i, phi_i) over the up (0) and the down (1)
+    electrons of each walker.  NaN rows for a walker with a non-finite coordinate."""
+    x = _check_cuda(x)
+    B, N, _ = x.shape
+    rho = torch.empty(B, 2, sf_nlm(lmax), 2, dtype=torch.float64, device=x.device)
+    _lib.check(_lib.load().dh_sf_multipoles(_ptr(x), B, N, int(n_up), int(lmax), _ptr(rho), _stream(x.device)))
+    return torch.view_as_complex(rho)
+
+
+def _sf_accumulate_packed(x: torch.Tensor, n_up: int, lmax: int, multipoles: bool):
+    """(out, lmax + 1, nlm): one float64 device buffer filled by dh_sf_accumulate, [pair sums
+    3 (lmax + 1), padded to even | rho sums 4 nlm (re, im), with multipoles | nvalid as int32]."""
+    x = _check_cuda(x)
+    B, N, _ = x.shape
+    lib = _lib.load()
+    nl, nlm = int(lmax) + 1, sf_nlm(lmax)
+    nbytes = int(lib.dh_sf_workspace_bytes(B, N, int(lmax)))
+    if nbytes < 1:
+        raise ValueError(f"structure_factor: B = {B}, N = {N} outside B >= 1, 1 <= N <= 32, B N < 2^31")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+    nrho = 4 * nlm if multipoles else 0
+    r0 = 3 * nl + (3 * nl) % 2  # an even offset: the complex view needs it
+    out = torch.zeros(r0 + nrho + 1, dtype=torch.float64, device=x.device)
+    pairs, rho, nvalid = out[:3 * nl], out[r0:r0 + nrho], out[r0 + nrho:]
+    _lib.check(lib.dh_sf_accumulate(_ptr(x), B, N, int(n_up), int(lmax), int(bool(multipoles)), _ptr(pairs),
+                                    _ptr(rho) if multipoles else None, _ptr(nvalid), _ptr(ws), ws.numel() * 8,
+                                    _stream(x.device)))
+    return out, nl, nlm
+
+
+def _sf_unpack(out: torch.Tensor, nl: int, nlm: int, multipoles: bool):
+    r0 = 3 * nl + (3 * nl) % 2
+    pairs = out[:3 * nl].reshape(3, nl)
+    rho = torch.view_as_complex(out[r0:r0 + 4 * nlm].reshape(2, nlm, 2)) if multipoles else None
+    return pairs, rho, int(out[-1:].view(torch.int32)[0].item())
+
+
+def sf_accumulate(x: torch.Tensor, n_up: int, lmax: int, multipoles: bool = True):
+    """(pair_sums[3, lmax + 1] float64, rho_sums[2, nlm] complex128 or None, nvalid): sf_pairs and
+    sf_multipoles summed over the walkers whose coordinates are all finite, without the per-walker
+    arrays; device tensors.  nvalid is read back from the device (one synchronisation)."""
+    out, nl, nlm = _sf_accumulate_packed(x, n_up, lmax, multipoles)
+    return _sf_unpack(out, nl, nlm, multipoles)
+
+
+def sf_accumulate_host(x: torch.Tensor, n_up: int, lmax: int, multipoles: bool = True):
+    """sf_accumulate's results as host tensors, brought over in one device read."""
+    out, nl, nlm = _sf_accumulate_packed(x, n_up, lmax, multipoles)
+    return _sf_unpack(out.cpu(), nl, nlm, multipoles)

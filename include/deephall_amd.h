@@ -517,6 +517,42 @@ int dh_spin_ratios(const float* logpsi, const float* logpsi_s, int B, int n_up, 
 int dh_spin_reduce(const float* logpsi, int B, int n_up, int n_dn, void* workspace, size_t workspace_bytes,
                    double* s2, double* pairs, double* total, int32_t* nvalid, void* stream);
 
+/* ---- Static structure factor S(L) from the walkers alone ---------------------------------------
+ * Walkers x[B][nelec][2] float32 (theta, phi); the slots below n_up are up electrons.  All
+ * arithmetic in double.  gamma_ij is the angle between electrons i and j,
+ *   cos gamma = cos th_i cos th_j + sin th_i sin th_j cos(ph_i - ph_j).
+ *
+ * dh_sf_pairs       T[B][3][lmax+1]: T[b][s][L] = sum over the pairs i < j of species s of
+ *                   P_L(cos gamma_ij); s = 0 both up, 1 i up and j down, 2 both down.  Row L = 0 is
+ *                   the pair count exactly; nothing is clamped (cos gamma = 1, -1 give 1, (-1)^L).
+ * dh_sf_multipoles  rho[B][2][nlm][2] (re, im): rho[b][a][lm] = sum over the electrons of species a
+ *                   (0 up, 1 down) of Y_LM(th, ph), 0 <= M <= L <= lmax, lm = L (L + 1) / 2 + M,
+ *                   nlm = dh_sf_nlm(lmax) = (lmax + 1)(lmax + 2) / 2.  Orthonormal Y_LM with the
+ *                   Condon-Shortley phase (Y_{L,-M} = (-1)^M conj Y_LM), by fully normalised
+ *                   recurrences: no overflow at any L <= DH_SF_MAX_L, and sin^M th underflowing to 0
+ *                   near a pole is the correct value.
+ *                   A walker is valid when its 2 nelec coordinates are all finite; both calls write
+ *                   NaN rows for an invalid one.
+ * dh_sf_accumulate  pair_sums[3][lmax+1] and (want_multipoles != 0) rho_sums[2][nlm][2]: the sums of
+ *                   the above over the valid walkers, and nvalid (one device int32), their number.
+ *                   Nothing per walker leaves the kernel: each workgroup adds a contiguous range of
+ *                   walkers in order into one partial in the workspace, a second kernel adds the
+ *                   partials in order.  No float atomics: two calls give identical bits, and
+ *                   pair_sums are the same bits with want_multipoles = 0, which skips the multipoles
+ *                   entirely (rho_sums may then be null and is not touched).  No valid walker:
+ *                   zero sums and nvalid = 0.
+ * workspace: dh_sf_workspace_bytes(B, nelec, lmax) device bytes, 8-byte aligned.  Checked before any
+ * device call, DH_EINVAL otherwise (dh_sf_nlm then returns -1, dh_sf_workspace_bytes 0): B >= 1,
+ * 1 <= nelec <= 32, B nelec < 2^31, 0 <= n_up <= nelec, 0 <= lmax <= DH_SF_MAX_L, non-null
+ * pointers, the workspace size.  No dh_handle, as for the swap kernels. */
+#define DH_SF_MAX_L 64
+int dh_sf_nlm(int lmax);
+size_t dh_sf_workspace_bytes(int B, int nelec, int lmax);
+int dh_sf_pairs(const float* x, int B, int nelec, int n_up, int lmax, double* T, void* stream);
+int dh_sf_multipoles(const float* x, int B, int nelec, int n_up, int lmax, double* rho, void* stream);
+int dh_sf_accumulate(const float* x, int B, int nelec, int n_up, int lmax, int want_multipoles, double* pair_sums,
+                     double* rho_sums, int32_t* nvalid, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- log psi supplied by the caller: the arbitrary-callable boundary ---------------------
  * The reference's make_mcmc_step(batch_network, ...) (mcmc.py:105-150) and
  * make_local_kinetic_energy(f, Q, r) (hamiltonian.py:83-172) accept ANY log psi.  For one
