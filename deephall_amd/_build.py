@@ -25,8 +25,9 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I", st
 # fused channel tail likewise (round 5: the packed form of layer 1's residual spilled 44 B per
 # lane; without it no spills, channel launches 440 -> 438 us, profiles/r05_v26_lnch_noslp_ab.txt)
 # sfactor.hip: no contraction, so its walker functions round alike in every kernel they are inlined into
+# quasihole.hip: no contraction, so its value and energy instantiations form the same bits of log psi
 EXTRA = {"gemm_x6.hip": ["-fno-slp-vectorize"], "gemm_lnch.hip": ["-fno-slp-vectorize"],
-         "sfactor.hip": ["-ffp-contract=off"]}
+         "sfactor.hip": ["-ffp-contract=off"], "quasihole.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -114,7 +114,12 @@ EXPORTS = [
     "dh_sf_pairs",
     "dh_sf_multipoles",
     "dh_sf_accumulate",
+    "dh_create_quasihole",
 ]
+
+DH_QUASIHOLE_MAX_HOLES = 8
+QUASIHOLE_BASES = {"halperin": 0, "pfaffian": 1}  # DH_QUASIHOLE_*
+HOLE_KINDS = {"both": 0, "up": 1, "down": 2, "A": 3, "B": 4}  # DH_HOLE_*
 
 DH_SWAP_MAX_ANGLES = 64
 DH_RDM_MAX_LEVELS = 4
@@ -149,6 +154,24 @@ class DhConfig(C.Structure):
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
         self.struct_size = C.sizeof(DhConfig)
+
+
+class DhQuasihole(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", C.c_int),
+        ("m_up", C.c_int),
+        ("m_dn", C.c_int),
+        ("n_inter", C.c_int),
+        ("p", C.c_int),
+        ("n_holes", C.c_int),
+        ("kind", C.c_int * DH_QUASIHOLE_MAX_HOLES),
+        ("holes", (C.c_double * 2) * DH_QUASIHOLE_MAX_HOLES),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(DhQuasihole)
 
 
 _lib = None
@@ -296,6 +319,8 @@ def load(path: Path | str | None = None):
     lib.dh_rdm_accumulate.restype = i32
     lib.dh_create_halperin.argtypes = [C.POINTER(DhConfig), i32, i32, i32, C.POINTER(vp)]
     lib.dh_create_halperin.restype = i32
+    lib.dh_create_quasihole.argtypes = [C.POINTER(DhConfig), C.POINTER(DhQuasihole), C.POINTER(vp)]
+    lib.dh_create_quasihole.restype = i32
     lib.dh_spin_workspace_bytes.argtypes = [i32, i32, i32]
     lib.dh_spin_workspace_bytes.restype = sz
     lib.dh_spin_exchange.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp]

@@ -45,6 +45,7 @@ class NetworkType(str, enum.Enum):
     jain = "jain"
     pfaffian = "pfaffian"
     halperin = "halperin"
+    quasihole = "quasihole"
 
 
 class OrbitalType(str, enum.Enum):
@@ -108,6 +109,30 @@ class HalperinNetwork:
 
 
 @dataclass
+class QuasiholeNetwork:
+    """Quasiholes pinned at chosen points (not in the reference; networks/quasihole.py).  ``base``:
+    "halperin" (exponents from ``network.halperin.exponents``; Laughlin 1/m is nspins (N, 0)) or
+    "pfaffian" (p from ``network.pfaffian.cf_flux``).  ``holes``: (theta, phi) pairs, at most 8.
+    ``species``: "both", "up" or "down" per hole, halperin base only; None is all "both".
+    ``pairing``: two equal-length tuples of hole indices, the groups A and B of the pfaffian base;
+    the holes not listed are Abelian.  The system's flux rises by one per hole that acts on a
+    species (halperin base), by one per pair of the groups and per Abelian hole (pfaffian base)."""
+
+    base: str = "halperin"
+    holes: tuple = ()
+    species: Optional[tuple] = None
+    pairing: Optional[tuple] = None
+
+    def __post_init__(self):  # lists from a config file
+        self.base = str(getattr(self.base, "value", self.base))
+        self.holes = tuple((float(t), float(p)) for t, p in self.holes)
+        if self.species is not None:
+            self.species = tuple(str(s) for s in self.species)
+        if self.pairing is not None:
+            self.pairing = tuple(tuple(int(a) for a in grp) for grp in self.pairing)
+
+
+@dataclass
 class Network:
     type: NetworkType = NetworkType.psiformer
     orbital: OrbitalType = OrbitalType.full
@@ -115,6 +140,7 @@ class Network:
     jain: JainNetwork = field(default_factory=JainNetwork)
     pfaffian: PfaffianNetwork = field(default_factory=PfaffianNetwork)
     halperin: HalperinNetwork = field(default_factory=HalperinNetwork)
+    quasihole: QuasiholeNetwork = field(default_factory=QuasiholeNetwork)
 
 
 @dataclass
@@ -175,9 +201,9 @@ class OptimizerMinsr:
 class Pretrain:
     """Fidelity pretraining onto a trial state before the energy minimisation (pretrain.py; not
     in the reference).  ``iterations``: 0 switches it off.  ``reference``: "laughlin", "jain",
-    "pfaffian" or "halperin", built for the run's system as the overlap estimator builds it
+    "pfaffian", "halperin" or "quasihole", built for the run's system as the overlap estimator builds it
     (``network.jain`` / ``network.pfaffian`` choose p and the occupation, ``network.halperin`` the
-    exponents).  ``lr``: None is the chosen optimizer's own
+    exponents, ``network.quasihole`` the base and the holes).  ``lr``: None is the chosen optimizer's own
     schedule; either way it starts at t = 0 and the training after it starts at t = 0 again."""
 
     iterations: int = 0

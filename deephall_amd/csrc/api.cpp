@@ -257,7 +257,99 @@ int create_halperin(const dh_config* cfg, int m_up, int m_dn, int n_int, dh_hand
   *out = h;
   return DH_OK;
 }
+
+// Pinned quasiholes (quasihole.hip) on a Halperin or a Pfaffian base: every hole adds one to the
+// degree of the electrons it acts on, a group of k holes k to the degree of every electron
+int create_quasihole(const dh_config* cfg, const dh_quasihole* q, dh_handle** out) {
+  const int N = cfg->n_up + cfg->n_dn;
+  const bool pf = q->base == DH_QUASIHOLE_PFAFFIAN;
+  if (q->base != DH_QUASIHOLE_HALPERIN && !pf)
+    return fail(DH_EINVAL, "Quasihole: base must be DH_QUASIHOLE_HALPERIN or DH_QUASIHOLE_PFAFFIAN, got " +
+                               std::to_string(q->base));
+  if (int rc = check_analytic(cfg, "Quasihole", pf ? 2 : 1)) return rc;
+  if (q->n_holes < 1 || q->n_holes > DH_QUASIHOLE_MAX_HOLES)
+    return fail(DH_EINVAL, "Quasihole: need 1 <= n_holes <= " + std::to_string(DH_QUASIHOLE_MAX_HOLES) + ", got " +
+                               std::to_string(q->n_holes) +
+                               (q->n_holes == 0 ? (pf ? " (without holes this is the pfaffian state: dh_create)"
+                                                      : " (without holes this is the halperin state: dh_create_halperin)")
+                                                : ""));
+  int count[5] = {0, 0, 0, 0, 0};
+  QuasiholeState st{};
+  st.pfaffian = pf;
+  st.n_holes = q->n_holes;
+  for (int a = 0; a < q->n_holes; ++a) {
+    const double th = q->holes[a][0], ph = q->holes[a][1];
+    const int kind = q->kind[a];
+    if (!std::isfinite(th) || !std::isfinite(ph))
+      return fail(DH_EINVAL, "Quasihole: hole " + std::to_string(a) + " has a non-finite angle");
+    if (th < 0.0 || th > M_PI)
+      return fail(DH_EINVAL, "Quasihole: hole " + std::to_string(a) + " needs 0 <= theta <= pi, got " + std::to_string(th));
+    const bool ok = pf ? (kind == DH_HOLE_BOTH || kind == DH_HOLE_GROUP_A || kind == DH_HOLE_GROUP_B)
+                       : (kind == DH_HOLE_BOTH || kind == DH_HOLE_UP || kind == DH_HOLE_DOWN);
+    if (!ok)
+      return fail(DH_EINVAL, "Quasihole: hole " + std::to_string(a) + " has kind " + std::to_string(kind) +
+                                 (pf ? ", the pfaffian base takes DH_HOLE_BOTH, DH_HOLE_GROUP_A and DH_HOLE_GROUP_B"
+                                     : ", the halperin base takes DH_HOLE_BOTH, DH_HOLE_UP and DH_HOLE_DOWN"));
+    ++count[kind];
+    st.kind[a] = kind;
+    st.uv[a][0] = std::cos(0.5 * th) * std::cos(0.5 * ph);
+    st.uv[a][1] = std::cos(0.5 * th) * std::sin(0.5 * ph);
+    st.uv[a][2] = std::sin(0.5 * th) * std::cos(0.5 * ph);
+    st.uv[a][3] = -std::sin(0.5 * th) * std::sin(0.5 * ph);
+  }
+  if (pf) {
+    const int p = q->p, k = count[DH_HOLE_GROUP_A];
+    if (N % 2) return fail(DH_EINVAL, "Quasihole: the pfaffian base needs an even number of electrons");
+    if (p < 1) return fail(DH_EINVAL, "Quasihole: the pfaffian base needs p >= 1, got " + std::to_string(p));
+    if (count[DH_HOLE_GROUP_B] != k)
+      return fail(DH_EINVAL, "Quasihole: the groups A and B need the same number of holes, got " + std::to_string(k) +
+                                 " and " + std::to_string(count[DH_HOLE_GROUP_B]));
+    const int64_t f = (int64_t)2 * p * (N - 1) - 1 + k + count[DH_HOLE_BOTH];
+    if (cfg->flux != f)
+      return fail(DH_EINVAL, "Quasihole: the state lives at flux 2 p (N - 1) - 1 + k + (Abelian holes) = " +
+                                 std::to_string(f) + ", got " + std::to_string(cfg->flux));
+    st.m_up = st.m_dn = st.n_int = 2 * p;
+  } else {
+    const int m_up = q->m_up, m_dn = q->m_dn, n_int = q->n_inter;
+    if (m_up < 1 || m_dn < 1 || m_up % 2 == 0 || m_dn % 2 == 0)
+      return fail(DH_EINVAL, "Quasihole: m_up and m_dn must be odd and >= 1, got " + std::to_string(m_up) + ", " +
+                                 std::to_string(m_dn));
+    if (n_int < 0) return fail(DH_EINVAL, "Quasihole: need n >= 0, got " + std::to_string(n_int));
+    const int h_up = count[DH_HOLE_BOTH] + count[DH_HOLE_UP], h_dn = count[DH_HOLE_BOTH] + count[DH_HOLE_DOWN];
+    const int64_t f_up = (int64_t)m_up * (cfg->n_up - 1) + (int64_t)n_int * cfg->n_dn + h_up;
+    const int64_t f_dn = (int64_t)m_dn * (cfg->n_dn - 1) + (int64_t)n_int * cfg->n_up + h_dn;
+    if (cfg->n_up > 0 && cfg->flux != f_up)
+      return fail(DH_EINVAL, "Quasihole: the up electrons live at flux m_up (n_up - 1) + n n_dn + h_up = " +
+                                 std::to_string(f_up) + ", got " + std::to_string(cfg->flux));
+    if (cfg->n_dn > 0 && cfg->flux != f_dn)
+      return fail(DH_EINVAL, "Quasihole: the down electrons live at flux m_dn (n_dn - 1) + n n_up + h_dn = " +
+                                 std::to_string(f_dn) + ", got " + std::to_string(cfg->flux));
+    st.m_up = m_up;
+    st.m_dn = m_dn;
+    st.n_int = n_int;
+  }
+  if (quasihole_smem_bytes(N, pf, true) > 160 * 1024)
+    return fail(DH_EINVAL, "Quasihole: N = " + std::to_string(N) + " needs " +
+                               std::to_string(quasihole_smem_bytes(N, pf, true)) +
+                               " bytes of LDS; the one-workgroup kernel has 160 KiB");
+  dh_handle* h = analytic_handle(cfg, dh_handle::QUASIHOLE, {});
+  h->quasihole = st;
+  *out = h;
+  return DH_OK;
+}
 }  // namespace
+
+int dh_create_quasihole(const dh_config* cfg, const dh_quasihole* q, dh_handle** out) {
+  if (!cfg || !q || !out) return fail(DH_EINVAL, "Quasihole: null argument");
+  if (cfg->struct_size != sizeof(dh_config))
+    return fail(DH_EINVAL, "Quasihole: dh_config.struct_size must equal sizeof(dh_config)");
+  if (q->struct_size != sizeof(dh_quasihole))
+    return fail(DH_EINVAL, "Quasihole: dh_quasihole.struct_size must equal sizeof(dh_quasihole) (" +
+                               std::to_string(sizeof(dh_quasihole)) + " bytes)");
+  if (cfg->network_type != DH_NETWORK_QUASIHOLE)
+    return fail(DH_EINVAL, "Quasihole: dh_create_quasihole needs network_type DH_NETWORK_QUASIHOLE");
+  return create_quasihole(cfg, q, out);
+}
 
 int dh_create_halperin(const dh_config* cfg, int m_up, int m_dn, int n_inter, dh_handle** out) {
   if (!cfg || !out) return fail(DH_EINVAL, "Halperin: null argument");
@@ -291,6 +383,8 @@ int dh_create(const dh_config* cfg, dh_handle** out) {
   if (cfg->network_type == DH_NETWORK_PFAFFIAN) return create_pfaffian(cfg, out);
   if (cfg->network_type == DH_NETWORK_HALPERIN)
     return fail(DH_EINVAL, "Halperin: the exponents (m_up, m_dn, n) are arguments of dh_create_halperin, not dh_create");
+  if (cfg->network_type == DH_NETWORK_QUASIHOLE)
+    return fail(DH_EINVAL, "Quasihole: the base and the holes are arguments of dh_create_quasihole, not dh_create");
   if (cfg->network_type != DH_NETWORK_PSIFORMER) return fail(DH_EINVAL, "bad network type");
   const int N = cfg->n_up + cfg->n_dn;
   if (cfg->n_up < 0 || cfg->n_dn < 0 || N < 1 || N > 32) return fail(DH_EINVAL, "need 1 <= N <= 32 electrons");
@@ -870,7 +964,9 @@ int launch_trial(dh_handle* h, const float* x, float* logpsi, float* e_l, float*
     HIP_TRY(hipMemcpy(h->expo, h->expo_host.data(), h->expo_host.size() * sizeof(int), hipMemcpyHostToDevice));
   }
   PROF(e_l ? PK_DET_ENERGY : PK_DET_VALUE, 0.0, e_l ? 48.0 * nw : 8.0 * nw * h->d.N);
-  if (h->state == dh_handle::HALPERIN)
+  if (h->state == dh_handle::QUASIHOLE)
+    launch_quasihole(h->d, x, h->quasihole, logpsi, e_l, obs, nw, s);
+  else if (h->state == dh_handle::HALPERIN)
     launch_halperin(h->d, x, h->halperin[0], h->halperin[1], h->halperin[2], logpsi, e_l, obs, nw, s);
   else if (h->state == dh_handle::PFAFFIAN)
     launch_pfaffian(h->d, x, h->cfg.cf_flux, logpsi, e_l, obs, nw, s);

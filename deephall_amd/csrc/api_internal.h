@@ -105,13 +105,14 @@ struct dh_handle {
   bool params_set = false;
   bool ref_set = false;
   // Which wavefunction the handle is.  All but the Psiformer are analytic: no parameters, one
-  // kernel file each (laughlin.hip, cf.hip, pfaffian.hip, halperin.hip), launched by launch_trial
-  enum State { PSIFORMER, LAUGHLIN, JAIN, PFAFFIAN, HALPERIN } state = PSIFORMER;
+  // kernel file each (laughlin.hip, cf.hip, pfaffian.hip, halperin.hip, quasihole.hip), launched by launch_trial
+  enum State { PSIFORMER, LAUGHLIN, JAIN, PFAFFIAN, HALPERIN, QUASIHOLE } state = PSIFORMER;
   bool analytic() const { return state != PSIFORMER; }
   int cf_dense = 0;               // Jain: the number of level-1 (dense) columns
   int halperin[3] = {0, 0, 0};    // Halperin: m_up, m_dn, n (arguments of dh_create_halperin, not dh_config fields)
+  dh::QuasiholeState quasihole{};  // Quasihole: the base's weights and the holes (dh_create_quasihole)
   std::vector<int> expo_host;     // Laughlin exponents [2][N] = (Q1 + m_j, Q1 - m_j); Jain: cf.hip's column table;
-                                  // Pfaffian, Halperin: empty
+                                  // Pfaffian, Halperin, Quasihole: empty
   int* expo = nullptr;            // device copy (uploaded at first use)
   dh::KfacHost* kfac = nullptr;   // KFAC plan (built at first dh_kfac_* call)
   dh::Profiler prof;

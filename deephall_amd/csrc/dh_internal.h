@@ -512,6 +512,20 @@ size_t halperin_smem_bytes(int N, bool energy);
 void launch_halperin(const Dims& d, const float* x, int m_up, int m_dn, int n_int, float* logpsi, float* e_l,
                      float* obs, int nw, hipStream_t s);
 
+// quasihole.hip: the same two launches for pinned quasiholes on a Halperin or a Moore-Read base.
+// The state goes to the kernel by value: the pair weights (Pfaffian base: all three 2 p), the
+// holes' kinds (DH_HOLE_*) and spinors (Re U, Im U, Re V, Im V).  LDS per walker by instantiation.
+struct QuasiholeState {
+  int pfaffian;  // 0: Halperin base, 1: Pfaffian base
+  int m_up, m_dn, n_int;
+  int n_holes;
+  int kind[DH_QUASIHOLE_MAX_HOLES];
+  double uv[DH_QUASIHOLE_MAX_HOLES][4];
+};
+size_t quasihole_smem_bytes(int N, bool pfaffian, bool energy);
+void launch_quasihole(const Dims& d, const float* x, const QuasiholeState& q, float* logpsi, float* e_l, float* obs,
+                      int nw, hipStream_t s);
+
 // det.hip: backward of log psi = J + log sum_k det Phi_k for per-walker cotangents ct[nw][2]:
 // dF [nw*N][ld_orb] (all columns written) and jg[nw][2] = ct.re * dJ / d(ee_par, ee_anti)
 void launch_det_bwd(const Dims& d, const float* F, const float* x, const float* jastrow, const float* norm,

@@ -3,7 +3,8 @@
 Both log-amplitudes are native (``dh_logpsi`` of the network and of the Laughlin state of
 the same system, or of the Jain state ``network.jain`` describes with
 ``estimator_options["reference"] = "jain"``, or of the Moore-Read state of ``network.pfaffian``
-with ``"pfaffian"``, or of the Halperin state of ``network.halperin`` with ``"halperin"``); ratio = exp(log phi - log psi - shift),
+with ``"pfaffian"``, or of the Halperin state of ``network.halperin`` with ``"halperin"``, or of the
+pinned-quasihole state of ``network.quasihole`` with ``"quasihole"``); ratio = exp(log phi - log psi - shift),
 shift = the walker mean of log phi - log psi; digest: |nanmean(ratio)|^2 / nanmean(|ratio|^2) over the steps.
 """
 
@@ -30,8 +31,9 @@ class OverlapEstimator(Estimator):
         super().__init__(adaptor, system, estimator_options, observable_options)
         cfg = adaptor.cfg
         reference = str((estimator_options or {}).get("reference", "laughlin"))
-        if reference not in ("laughlin", "jain", "pfaffian", "halperin"):
-            raise ValueError(f"overlap: reference must be 'laughlin', 'jain', 'pfaffian' or 'halperin', got {reference!r}")
+        if reference not in ("laughlin", "jain", "pfaffian", "halperin", "quasihole"):
+            raise ValueError("overlap: reference must be 'laughlin', 'jain', 'pfaffian', 'halperin' or 'quasihole', "
+                             f"got {reference!r}")
         self.laughlin = make_network(cfg.system, dataclasses.replace(cfg.network, type=NetworkType(reference)))
 
     def empty_val_state(self, steps: int):

@@ -8,6 +8,7 @@ from .jain import Jain, JainCallable
 from .laughlin import Laughlin, LaughlinQuasiparticle
 from .pfaffian import MooreRead, MooreReadCallable
 from .psiformer import Psiformer
+from .quasihole import Quasihole, QuasiholeCallable
 
 
 def make_network(system: System, network: Network) -> Psiformer:
@@ -23,6 +24,11 @@ def make_network(system: System, network: Network) -> Psiformer:
         return MooreRead(flux=system.flux, nspins=system.nspins, cf_flux=network.pfaffian.cf_flux, system=system)
     if ntype == NetworkType.halperin.value:  # halperin.hip: (m_up, m_dn, n) on the two species of nspins
         return Halperin(flux=system.flux, nspins=system.nspins, exponents=network.halperin.exponents, system=system)
+    if ntype == NetworkType.quasihole.value:  # quasihole.hip: pinned holes on the halperin or the pfaffian base
+        q = network.quasihole
+        return Quasihole(flux=system.flux, nspins=system.nspins, base=q.base, holes=q.holes, species=q.species,
+                         pairing=q.pairing, exponents=network.halperin.exponents, cf_flux=network.pfaffian.cf_flux,
+                         system=system)
     if ntype == NetworkType.psiformer.value:
         return Psiformer(
             Q=Q,
@@ -38,4 +44,5 @@ def make_network(system: System, network: Network) -> Psiformer:
 
 
 __all__ = ["make_network", "Psiformer", "Laughlin", "LaughlinQuasiparticle", "Jain", "JainCallable",
-           "MooreRead", "MooreReadCallable", "Halperin", "HalperinCallable"]
+           "MooreRead", "MooreReadCallable", "Halperin", "HalperinCallable",
+           "Quasihole", "QuasiholeCallable"]

@@ -60,6 +60,8 @@ class NetworkSpec:
     cf_flux: int = 1
     occupation: tuple | None = None  # jain: ((Lambda level, 2 m), ...) ints; None: the filled-levels ground state
     halperin: tuple | None = None  # halperin: (m_up, m_dn, n) ints, the arguments of dh_create_halperin
+    # quasihole: (base, (m_up, m_dn, n), p, ((theta, phi, kind), ...)), the fields of dh_quasihole
+    quasihole: tuple | None = None
 
     @property
     def nelec(self) -> int:
@@ -83,11 +85,34 @@ class NetworkSpec:
         c.num_heads, c.heads_dim, c.num_layers = self.num_heads, self.heads_dim, self.num_layers
         c.ndets = self.ndets
         c.orbital_type = {"full": 0, "sparse": 1}.get(str(getattr(self.orbital_type, "value", self.orbital_type)), -1)
-        c.network_type = {"psiformer": 0, "laughlin": 1, "jain": 2, "pfaffian": 3, "halperin": 4}.get(
+        c.network_type = {"psiformer": 0, "laughlin": 1, "jain": 2, "pfaffian": 3, "halperin": 4, "quasihole": 5}.get(
             str(getattr(self.network_type, "value", self.network_type)), -1)
         c.excitation_lz = float(self.excitation_lz)
         c.cf_flux = int(self.cf_flux)
         return c
+
+    def quasihole_c(self) -> _lib.DhQuasihole:
+        base, (m_up, m_dn, n), p, holes = self.quasihole
+        q = _lib.DhQuasihole()
+        q.base = _lib.QUASIHOLE_BASES[base]
+        q.m_up, q.m_dn, q.n_inter, q.p = int(m_up), int(m_dn), int(n), int(p)
+        q.n_holes = len(holes)
+        for a, (theta, phi, kind) in enumerate(holes):
+            q.holes[a][0], q.holes[a][1] = float(theta), float(phi)
+            q.kind[a] = _lib.HOLE_KINDS[kind]
+        return q
+
+    def create(self, lib, handle) -> int:
+        """The dh_create* call of this spec into ``handle`` (a c_void_p); the library's return code."""
+        cfg = self.to_c()
+        if self.occupation is not None:
+            occ = (C.c_int * (2 * len(self.occupation)))(*[int(v) for pair in self.occupation for v in pair])
+            return lib.dh_create_cf(C.byref(cfg), occ, len(self.occupation), C.byref(handle))
+        if self.halperin is not None:
+            return lib.dh_create_halperin(C.byref(cfg), *(int(e) for e in self.halperin), C.byref(handle))
+        if self.quasihole is not None:
+            return lib.dh_create_quasihole(C.byref(cfg), C.byref(self.quasihole_c()), C.byref(handle))
+        return lib.dh_create(C.byref(cfg), C.byref(handle))
 
 
 class NativeHandle:
@@ -98,14 +123,7 @@ class NativeHandle:
         self.spec = spec
         self.device = device
         self.h = C.c_void_p()
-        cfg = spec.to_c()
-        if spec.occupation is not None:
-            occ = (C.c_int * (2 * len(spec.occupation)))(*[int(v) for pair in spec.occupation for v in pair])
-            _lib.check(self.lib.dh_create_cf(C.byref(cfg), occ, len(spec.occupation), C.byref(self.h)))
-        elif spec.halperin is not None:
-            _lib.check(self.lib.dh_create_halperin(C.byref(cfg), *(int(e) for e in spec.halperin), C.byref(self.h)))
-        else:
-            _lib.check(self.lib.dh_create(C.byref(cfg), C.byref(self.h)))
+        _lib.check(spec.create(self.lib, self.h))
         nseg = self.lib.dh_ref_layout(self.h, None, 0)
         offs = (C.c_size_t * (nseg + 1))()
         self.lib.dh_ref_layout(self.h, offs, nseg + 1)
@@ -197,8 +215,8 @@ def flatten_params(params) -> dict:
 
 def param_shapes(spec: NetworkSpec) -> dict:
     """Shapes of the reference's parameter tree (Flax auto-naming)."""
-    if spec.network_type in ("laughlin", "jain", "pfaffian", "halperin"):
-        return {}  # laughlin.py has no parameters; neither have the Jain, Moore-Read and Halperin states
+    if spec.network_type in ("laughlin", "jain", "pfaffian", "halperin", "quasihole"):
+        return {}  # laughlin.py has no parameters; neither have the Jain, Moore-Read, Halperin and quasihole states
     D, H, dh = spec.D, spec.num_heads, spec.heads_dim
     M, N, K = spec.M, spec.nelec, spec.ndets
     p = "PsiformerLayers_0/"

@@ -1,6 +1,6 @@
 """Fidelity pretraining: pull the randomly initialised Psiformer onto an analytic trial state
 before the energy minimisation (not in the reference; FermiNet and Psiformer pretrain on
-Hartree-Fock, here the native Laughlin, Jain, Moore-Read and Halperin states play that role).
+Hartree-Fock, here the native Laughlin, Jain, Moore-Read, Halperin and quasihole states play that role).
 
 Walkers x_b come from |psi|^2 (the existing dh_mcmc_step); phi is the trial state,
 d_b = log phi(x_b) - log psi(x_b), r_b = e^{d_b}:
@@ -37,7 +37,7 @@ from .networks.psiformer import _ptr, _stream
 
 logger = logging.getLogger("deephall_amd")
 
-REFERENCES = ("laughlin", "jain", "pfaffian", "halperin")
+REFERENCES = ("laughlin", "jain", "pfaffian", "halperin", "quasihole")
 
 
 def _check_logs(logpsi: torch.Tensor, logphi: torch.Tensor):
@@ -160,15 +160,7 @@ def make_reference(cfg: Config):
     # dh_create is host code: the same refusal a device handle would meet later
     lib = _lib.load()
     h = C.c_void_p()
-    c = ref.spec.to_c()
-    occ = ref.spec.occupation
-    if occ is not None:
-        arr = (C.c_int * (2 * len(occ)))(*[int(v) for pair in occ for v in pair])
-        rc = lib.dh_create_cf(C.byref(c), arr, len(occ), C.byref(h))
-    elif ref.spec.halperin is not None:
-        rc = lib.dh_create_halperin(C.byref(c), *(int(e) for e in ref.spec.halperin), C.byref(h))
-    else:
-        rc = lib.dh_create(C.byref(c), C.byref(h))
+    rc = ref.spec.create(lib, h)
     if rc != 0:
         raise ValueError(f"optim.pretrain: no {name} trial state at {where}: "
                          f"{lib.dh_last_error().decode(errors='replace')}")

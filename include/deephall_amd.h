@@ -60,6 +60,8 @@ extern "C" {
                                 flux = 2 p (N - 1) - 1 exactly (nu = 1/2 at p = 1); N <= 28 by the kernel's LDS */
 #define DH_NETWORK_HALPERIN 4 /* Halperin (m_up, m_dn, n) two-component state (no parameters): dh_create_halperin
                                 only; dh_create refuses the type, the exponents are not dh_config fields */
+#define DH_NETWORK_QUASIHOLE 5 /* pinned quasiholes on a Halperin / Laughlin or a Moore-Read base (no parameters):
+                                 dh_create_quasihole only; dh_create refuses the type */
 #define DH_ORBITAL_FULL 0
 #define DH_ORBITAL_SPARSE 1 /* blocks.py:52-62: 8 features per (j, k) mixed into the M harmonics by
                                lll_weight; folded into the full layout when parameters are set */
@@ -105,6 +107,41 @@ int dh_create_cf(const dh_config* cfg, const int* occ, int n_occ, dh_handle** ou
  * species is bound by its parity only); anything else is DH_EINVAL with a message that starts
  * "Halperin".  The handle has no parameters and serves the calls a dh_create_cf handle serves. */
 int dh_create_halperin(const dh_config* cfg, int m_up, int m_dn, int n_inter, dh_handle** out);
+
+/* Pinned quasiholes (cfg->network_type = DH_NETWORK_QUASIHOLE).  Hole a at (theta_a, phi_a) has the
+ * spinor (U_a, V_a) of an electron there and s_a(i) = u_i V_a - v_i U_a, zero with electron i on it.
+ *   base DH_QUASIHOLE_HALPERIN: log psi = sum_{i<k} c_ik log w_ik + sum_a sum_{i in S_a} log s_a(i),
+ *     c_ik as for dh_create_halperin; S_a all electrons (DH_HOLE_BOTH), the up slots (DH_HOLE_UP) or
+ *     the down slots (DH_HOLE_DOWN); with h_up / h_dn holes acting on a species, a non-empty species
+ *     needs flux = m_up (n_up - 1) + n_inter n_dn + h_up = m_dn (n_dn - 1) + n_inter n_up + h_dn.
+ *     Laughlin 1/m: nspins (N, 0), exponents (m, any odd, 0).
+ *   base DH_QUASIHOLE_PFAFFIAN: the holes of kind DH_HOLE_GROUP_A and DH_HOLE_GROUP_B (k of each),
+ *     F_i = prod_{a in A} s_a(i), G_i = prod_{b in B} s_b(i), A_ik = (F_i G_k + F_k G_i) / w_ik,
+ *     log psi = log Pf(A) + 2 p sum_{i<k} log w_ik + sum_{a of DH_HOLE_BOTH} sum_i log s_a(i),
+ *     N even, flux = 2 p (N - 1) - 1 + k + (number of DH_HOLE_BOTH holes); N <= 28 by the kernel's LDS;
+ *     k = 0 (DH_HOLE_BOTH holes only): A_ik = 1 / w_ik, Moore-Read's own entries.
+ * No normalisation, Im log psi the principal phase.  1 <= n_holes <= DH_QUASIHOLE_MAX_HOLES, angles
+ * finite, 0 <= theta <= pi, flux <= 126, N <= 32; anything else is DH_EINVAL with a message that
+ * starts "Quasihole", before any launch.  The handle has no parameters and serves the calls a
+ * dh_create_halperin handle serves. */
+#define DH_QUASIHOLE_MAX_HOLES 8
+#define DH_QUASIHOLE_HALPERIN 0
+#define DH_QUASIHOLE_PFAFFIAN 1
+#define DH_HOLE_BOTH 0
+#define DH_HOLE_UP 1
+#define DH_HOLE_DOWN 2
+#define DH_HOLE_GROUP_A 3
+#define DH_HOLE_GROUP_B 4
+typedef struct dh_quasihole {
+  uint32_t struct_size;                     /* = sizeof(dh_quasihole) = 192 bytes                  */
+  int base;                                 /* DH_QUASIHOLE_HALPERIN or DH_QUASIHOLE_PFAFFIAN      */
+  int m_up, m_dn, n_inter;                  /* Halperin base: the exponents                        */
+  int p;                                    /* Pfaffian base: 2 p vortices per electron            */
+  int n_holes;
+  int kind[DH_QUASIHOLE_MAX_HOLES];         /* DH_HOLE_* of hole a                                 */
+  double holes[DH_QUASIHOLE_MAX_HOLES][2];  /* (theta, phi) of hole a                              */
+} dh_quasihole;
+int dh_create_quasihole(const dh_config* cfg, const dh_quasihole* q, dh_handle** out);
 void dh_destroy(dh_handle* h);
 const char* dh_last_error(void);
 const char* dh_version(void);
