@@ -59,333 +59,17 @@ Work carve(const Dims& d, int gemm_mode, int nw, int C, void* base) {
 
 }  // namespace
 
-// The kernel classes of the profiler's records (Profiler, PROF: api_internal.h)
-enum ProfKind { PK_GEMM = 0, PK_ATTN, PK_LN, PK_INPUT, PK_DET_VALUE, PK_DET_ENERGY, PK_MCMC, PK_COUNT };
-// channel-mode (C > 1) launches of GEMM/attention/LayerNorm/input are recorded as kind + PK_CH;
-// PK_L1CH: the local energy's layer 1 in one launch (gemm_lnch MODE 2)
-constexpr int PK_CH = PK_COUNT, PK_L1CH = PK_COUNT + 4, PK_TOTAL = PK_COUNT + 5;
-
 extern "C" {
 
 const char* dh_last_error(void) { return g_err.c_str(); }
 const char* dh_version(void) { return "deephall_amd 0.1 (gfx950)"; }
-
-namespace {
-// What every analytic state asks of N, the flux and the interaction; name starts the messages
-int check_analytic(const dh_config* cfg, const std::string& name, int n_min) {
-  const int N = cfg->n_up + cfg->n_dn;
-  if (cfg->n_up < 0 || cfg->n_dn < 0 || N < n_min || N > 32)
-    return fail(DH_EINVAL, name + ": need " + std::to_string(n_min) + " <= N <= 32 electrons");
-  if (cfg->flux < 1 || cfg->flux > 126) return fail(DH_EINVAL, name + " needs 1 <= flux <= 126");
-  if (cfg->interaction_type != DH_INTERACTION_COULOMB && cfg->interaction_type != DH_INTERACTION_HARMONIC)
-    return fail(DH_EINVAL, name + ": bad interaction type");
-  return DH_OK;
-}
-
-// Laughlin(nspins, flux, cf_flux, excitation_lz) (laughlin.py:19-46): exponents of the
-// composite-fermion orbitals, in doubled units (2 Q1, 2 m are integers)
-int laughlin_exponents(const dh_config* cfg, std::vector<int>& ex) {
-  const int N = cfg->n_up + cfg->n_dn;
-  const int p = cfg->cf_flux < 1 ? 1 : cfg->cf_flux;
-  const int q2 = cfg->flux - 2 * p * (N - 1);  // 2 Q1
-  if (q2 < 0) return fail(DH_EINVAL, "Laughlin: flux too small for N electrons (Q1 < 0)");
-  std::vector<int> m2;  // 2 m
-  if (N == q2 + 1) {  // ground state
-    for (int m = -q2; m <= q2; m += 2) m2.push_back(m);
-  } else if (N == q2) {  // quasihole: m = -Q1 .. Q1 without -lz (laughlin.py:66-73)
-    const double lz2 = 2.0 * cfg->excitation_lz;
-    const int l2 = (int)std::lround(lz2);
-    if (std::fabs(lz2 - l2) > 1e-6 || ((l2 - q2) % 2) != 0 || std::abs(l2) > q2)
-      return fail(DH_EINVAL, "Laughlin quasihole: impossible excitation_lz");
-    for (int m = -q2; m < -l2; m += 2) m2.push_back(m);
-    for (int m = q2; m > -l2; m -= 2) m2.push_back(m);
-  } else if (N == q2 + 2) {  // quasiparticle: m = -Q1 .. Q1, then the excited orbital (laughlin.py:82-100)
-    const double lz2 = 2.0 * cfg->excitation_lz;
-    const int l2 = (int)std::lround(lz2);
-    if (std::fabs(lz2 - l2) > 1e-6 || ((l2 - q2) % 2) != 0 || std::abs(l2) > q2 + 2)
-      return fail(DH_EINVAL, "Laughlin quasiparticle: impossible excitation_lz");
-    for (int m = -q2; m <= q2; m += 2) m2.push_back(m);
-    m2.push_back(l2);  // last column: A = Q1 + m1, B = Q1 - m1 (each >= -1)
-  } else {
-    return fail(DH_EINVAL, "Laughlin: filling not supported");
-  }
-  if ((int)m2.size() != N) return fail(DH_EINVAL, "Laughlin: orbital count mismatch");
-  ex.assign(2 * N + 1, 0);
-  for (int j = 0; j < N; ++j) {
-    ex[j] = (q2 + m2[j]) / 2;
-    ex[N + j] = (q2 - m2[j]) / 2;
-  }
-  ex[2 * N] = N == q2 + 2 ? 1 : 0;  // the kernel's quasiparticle flag
-  if (laughlin_smem_bytes(N) > 160 * 1024)
-    return fail(DH_EINVAL, "Laughlin: N too large for the one-workgroup kernel's LDS (160 KiB)");
-  return DH_OK;
-}
-// The handle of a parameter-free analytic state: no network dimensions
-dh_handle* analytic_handle(const dh_config* cfg, dh_handle::State state, const std::vector<int>& ex) {
-  const int N = cfg->n_up + cfg->n_dn;
-  auto* h = new dh_handle();
-  h->cfg = *cfg;
-  h->state = state;
-  h->expo_host = ex;
-  Dims& d = h->d;
-  d = Dims{};
-  d.N = N;
-  d.n_up = cfg->n_up;
-  d.n_dn = cfg->n_dn;
-  d.T = 2 * N;
-  d.C = 2 * N + 5;
-  d.M = 1;
-  d.Q = 0.5f * cfg->flux;
-  d.r = cfg->radius > 0.f ? cfg->radius : std::sqrt(d.Q);
-  d.H = 1;
-  d.dh = 4;
-  d.D = 4;
-  d.L = 0;
-  d.K = 1;
-  d.NB = 1;
-  d.orb_cols = 0;
-  d.ld_orb = 0;
-  d.interaction = cfg->interaction_type;
-  d.lambda = cfg->interaction_strength;
-  h->offsets = {0};
-  h->ref_offsets = {0};
-  h->params_set = h->ref_set = true;  // nothing to upload
-  return h;
-}
-
-// Jain state with two Lambda levels (cf.hip).  occ: [n_occ][2] = (level, 2 m), or null for the
-// ground state with both levels filled (N = 4 Q1 + 4: all of level 0, then all of level 1, m
-// ascending).  Fills the kernel's column table.
-int jain_table(const dh_config* cfg, const int* occ, int n_occ, std::vector<int>& tab, int& n_dense) {
-  const int N = cfg->n_up + cfg->n_dn;
-  const int p = cfg->cf_flux < 1 ? 1 : cfg->cf_flux;
-  const int q2 = cfg->flux - 2 * p * (N - 1);  // 2 Q1
-  if (q2 < 0) return fail(DH_EINVAL, "Jain: flux too small for N electrons (Q1 < 0)");
-  std::vector<int> lev, m2;
-  if (!occ) {
-    if (N != 2 * q2 + 4)
-      return fail(DH_EINVAL, "Jain: no ground state of two filled levels at this filling (needs N = 4 Q1 + 4)");
-    for (int n = 0; n < 2; ++n)
-      for (int m = -q2 - 2 * n; m <= q2 + 2 * n; m += 2) {
-        lev.push_back(n);
-        m2.push_back(m);
-      }
-  } else {
-    if (n_occ != N) return fail(DH_EINVAL, "Jain: the occupation needs one orbital per electron (n_occ = N)");
-    for (int j = 0; j < N; ++j) {
-      const int n = occ[2 * j], m = occ[2 * j + 1];
-      if (n != 0 && n != 1) return fail(DH_EINVAL, "Jain: Lambda level must be 0 or 1");
-      if (((m - q2) % 2) != 0) return fail(DH_EINVAL, "Jain: 2 m must have the parity of 2 Q1");
-      if (std::abs(m) > q2 + 2 * n) return fail(DH_EINVAL, "Jain: |m| > Q1 + level");
-      for (int k = 0; k < j; ++k)
-        if (lev[k] == n && m2[k] == m) return fail(DH_EINVAL, "Jain: orbital occupied twice");
-      lev.push_back(n);
-      m2.push_back(m);
-    }
-  }
-  n_dense = 0;
-  tab.assign(3 * N + 2, 0);
-  for (int j = 0; j < N; ++j) {
-    tab[3 * j] = lev[j];
-    tab[3 * j + 1] = (q2 + m2[j]) / 2;  // A >= -1
-    tab[3 * j + 2] = (q2 - m2[j]) / 2;  // B >= -1
-    if (lev[j]) {
-      tab.push_back(j);
-      ++n_dense;
-    }
-  }
-  tab[3 * N] = n_dense;
-  tab[3 * N + 1] = p;
-  if (cf_smem_bytes(N, n_dense, true) > 160 * 1024)
-    return fail(DH_EINVAL, "Jain: N and the number of level-1 orbitals need " +
-                               std::to_string(cf_smem_bytes(N, n_dense, true)) +
-                               " bytes of LDS; the one-workgroup kernel has 160 KiB");
-  return DH_OK;
-}
-
-int create_jain(const dh_config* cfg, const int* occ, int n_occ, dh_handle** out) {
-  if (int rc = check_analytic(cfg, "Jain", 1)) return rc;
-  std::vector<int> tab;
-  int n_dense = 0;
-  if (int rc = jain_table(cfg, occ, n_occ, tab, n_dense)) return rc;
-  dh_handle* h = analytic_handle(cfg, dh_handle::JAIN, tab);
-  h->cf_dense = n_dense;
-  *out = h;
-  return DH_OK;
-}
-
-// Moore-Read Pfaffian (pfaffian.hip): N even at flux 2 p (N - 1) - 1, nothing else to choose
-int create_pfaffian(const dh_config* cfg, dh_handle** out) {
-  const int N = cfg->n_up + cfg->n_dn, p = cfg->cf_flux;
-  if (int rc = check_analytic(cfg, "Pfaffian", 2)) return rc;
-  if (N % 2) return fail(DH_EINVAL, "Pfaffian: the paired state needs an even number of electrons");
-  if (p < 1) return fail(DH_EINVAL, "Pfaffian: need cf_flux >= 1");
-  if (cfg->flux != 2 * p * (N - 1) - 1)
-    return fail(DH_EINVAL, "Pfaffian: the state lives at flux 2 cf_flux (N - 1) - 1 = " +
-                               std::to_string(2 * p * (N - 1) - 1) + ", got " + std::to_string(cfg->flux));
-  if (pfaffian_smem_bytes(N, true) > 160 * 1024)
-    return fail(DH_EINVAL, "Pfaffian: N = " + std::to_string(N) + " needs " + std::to_string(pfaffian_smem_bytes(N, true)) +
-                               " bytes of LDS; the one-workgroup kernel has 160 KiB");
-  *out = analytic_handle(cfg, dh_handle::PFAFFIAN, {});
-  return DH_OK;
-}
-
-// Halperin (m_up, m_dn, n) (halperin.hip): both species at the flux of their degree in (u, v);
-// the exponent of an empty or single-electron species is free beyond its parity
-int create_halperin(const dh_config* cfg, int m_up, int m_dn, int n_int, dh_handle** out) {
-  const int N = cfg->n_up + cfg->n_dn;
-  if (int rc = check_analytic(cfg, "Halperin", 1)) return rc;
-  if (m_up < 1 || m_dn < 1 || m_up % 2 == 0 || m_dn % 2 == 0)
-    return fail(DH_EINVAL, "Halperin: m_up and m_dn must be odd and >= 1, got " + std::to_string(m_up) + ", " +
-                               std::to_string(m_dn));
-  if (n_int < 0) return fail(DH_EINVAL, "Halperin: need n >= 0, got " + std::to_string(n_int));
-  const int64_t f_up = (int64_t)m_up * (cfg->n_up - 1) + (int64_t)n_int * cfg->n_dn;
-  const int64_t f_dn = (int64_t)m_dn * (cfg->n_dn - 1) + (int64_t)n_int * cfg->n_up;
-  if (cfg->n_up > 0 && cfg->flux != f_up)
-    return fail(DH_EINVAL, "Halperin: the up electrons live at flux m_up (n_up - 1) + n n_dn = " + std::to_string(f_up) +
-                               ", got " + std::to_string(cfg->flux));
-  if (cfg->n_dn > 0 && cfg->flux != f_dn)
-    return fail(DH_EINVAL, "Halperin: the down electrons live at flux m_dn (n_dn - 1) + n n_up = " +
-                               std::to_string(f_dn) + ", got " + std::to_string(cfg->flux));
-  if (halperin_smem_bytes(N, true) > 160 * 1024)
-    return fail(DH_EINVAL, "Halperin: N = " + std::to_string(N) + " needs " + std::to_string(halperin_smem_bytes(N, true)) +
-                               " bytes of LDS; the one-workgroup kernel has 160 KiB");
-  dh_handle* h = analytic_handle(cfg, dh_handle::HALPERIN, {});
-  h->halperin[0] = m_up;
-  h->halperin[1] = m_dn;
-  h->halperin[2] = n_int;
-  *out = h;
-  return DH_OK;
-}
-
-// Pinned quasiholes (quasihole.hip) on a Halperin or a Pfaffian base: every hole adds one to the
-// degree of the electrons it acts on, a group of k holes k to the degree of every electron
-int create_quasihole(const dh_config* cfg, const dh_quasihole* q, dh_handle** out) {
-  const int N = cfg->n_up + cfg->n_dn;
-  const bool pf = q->base == DH_QUASIHOLE_PFAFFIAN;
-  if (q->base != DH_QUASIHOLE_HALPERIN && !pf)
-    return fail(DH_EINVAL, "Quasihole: base must be DH_QUASIHOLE_HALPERIN or DH_QUASIHOLE_PFAFFIAN, got " +
-                               std::to_string(q->base));
-  if (int rc = check_analytic(cfg, "Quasihole", pf ? 2 : 1)) return rc;
-  if (q->n_holes < 1 || q->n_holes > DH_QUASIHOLE_MAX_HOLES)
-    return fail(DH_EINVAL, "Quasihole: need 1 <= n_holes <= " + std::to_string(DH_QUASIHOLE_MAX_HOLES) + ", got " +
-                               std::to_string(q->n_holes) +
-                               (q->n_holes == 0 ? (pf ? " (without holes this is the pfaffian state: dh_create)"
-                                                      : " (without holes this is the halperin state: dh_create_halperin)")
-                                                : ""));
-  int count[5] = {0, 0, 0, 0, 0};
-  QuasiholeState st{};
-  st.pfaffian = pf;
-  st.n_holes = q->n_holes;
-  for (int a = 0; a < q->n_holes; ++a) {
-    const double th = q->holes[a][0], ph = q->holes[a][1];
-    const int kind = q->kind[a];
-    if (!std::isfinite(th) || !std::isfinite(ph))
-      return fail(DH_EINVAL, "Quasihole: hole " + std::to_string(a) + " has a non-finite angle");
-    if (th < 0.0 || th > M_PI)
-      return fail(DH_EINVAL, "Quasihole: hole " + std::to_string(a) + " needs 0 <= theta <= pi, got " + std::to_string(th));
-    const bool ok = pf ? (kind == DH_HOLE_BOTH || kind == DH_HOLE_GROUP_A || kind == DH_HOLE_GROUP_B)
-                       : (kind == DH_HOLE_BOTH || kind == DH_HOLE_UP || kind == DH_HOLE_DOWN);
-    if (!ok)
-      return fail(DH_EINVAL, "Quasihole: hole " + std::to_string(a) + " has kind " + std::to_string(kind) +
-                                 (pf ? ", the pfaffian base takes DH_HOLE_BOTH, DH_HOLE_GROUP_A and DH_HOLE_GROUP_B"
-                                     : ", the halperin base takes DH_HOLE_BOTH, DH_HOLE_UP and DH_HOLE_DOWN"));
-    ++count[kind];
-    st.kind[a] = kind;
-    st.uv[a][0] = std::cos(0.5 * th) * std::cos(0.5 * ph);
-    st.uv[a][1] = std::cos(0.5 * th) * std::sin(0.5 * ph);
-    st.uv[a][2] = std::sin(0.5 * th) * std::cos(0.5 * ph);
-    st.uv[a][3] = -std::sin(0.5 * th) * std::sin(0.5 * ph);
-  }
-  if (pf) {
-    const int p = q->p, k = count[DH_HOLE_GROUP_A];
-    if (N % 2) return fail(DH_EINVAL, "Quasihole: the pfaffian base needs an even number of electrons");
-    if (p < 1) return fail(DH_EINVAL, "Quasihole: the pfaffian base needs p >= 1, got " + std::to_string(p));
-    if (count[DH_HOLE_GROUP_B] != k)
-      return fail(DH_EINVAL, "Quasihole: the groups A and B need the same number of holes, got " + std::to_string(k) +
-                                 " and " + std::to_string(count[DH_HOLE_GROUP_B]));
-    const int64_t f = (int64_t)2 * p * (N - 1) - 1 + k + count[DH_HOLE_BOTH];
-    if (cfg->flux != f)
-      return fail(DH_EINVAL, "Quasihole: the state lives at flux 2 p (N - 1) - 1 + k + (Abelian holes) = " +
-                                 std::to_string(f) + ", got " + std::to_string(cfg->flux));
-    st.m_up = st.m_dn = st.n_int = 2 * p;
-  } else {
-    const int m_up = q->m_up, m_dn = q->m_dn, n_int = q->n_inter;
-    if (m_up < 1 || m_dn < 1 || m_up % 2 == 0 || m_dn % 2 == 0)
-      return fail(DH_EINVAL, "Quasihole: m_up and m_dn must be odd and >= 1, got " + std::to_string(m_up) + ", " +
-                                 std::to_string(m_dn));
-    if (n_int < 0) return fail(DH_EINVAL, "Quasihole: need n >= 0, got " + std::to_string(n_int));
-    const int h_up = count[DH_HOLE_BOTH] + count[DH_HOLE_UP], h_dn = count[DH_HOLE_BOTH] + count[DH_HOLE_DOWN];
-    const int64_t f_up = (int64_t)m_up * (cfg->n_up - 1) + (int64_t)n_int * cfg->n_dn + h_up;
-    const int64_t f_dn = (int64_t)m_dn * (cfg->n_dn - 1) + (int64_t)n_int * cfg->n_up + h_dn;
-    if (cfg->n_up > 0 && cfg->flux != f_up)
-      return fail(DH_EINVAL, "Quasihole: the up electrons live at flux m_up (n_up - 1) + n n_dn + h_up = " +
-                                 std::to_string(f_up) + ", got " + std::to_string(cfg->flux));
-    if (cfg->n_dn > 0 && cfg->flux != f_dn)
-      return fail(DH_EINVAL, "Quasihole: the down electrons live at flux m_dn (n_dn - 1) + n n_up + h_dn = " +
-                                 std::to_string(f_dn) + ", got " + std::to_string(cfg->flux));
-    st.m_up = m_up;
-    st.m_dn = m_dn;
-    st.n_int = n_int;
-  }
-  if (quasihole_smem_bytes(N, pf, true) > 160 * 1024)
-    return fail(DH_EINVAL, "Quasihole: N = " + std::to_string(N) + " needs " +
-                               std::to_string(quasihole_smem_bytes(N, pf, true)) +
-                               " bytes of LDS; the one-workgroup kernel has 160 KiB");
-  dh_handle* h = analytic_handle(cfg, dh_handle::QUASIHOLE, {});
-  h->quasihole = st;
-  *out = h;
-  return DH_OK;
-}
-}  // namespace
-
-int dh_create_quasihole(const dh_config* cfg, const dh_quasihole* q, dh_handle** out) {
-  if (!cfg || !q || !out) return fail(DH_EINVAL, "Quasihole: null argument");
-  if (cfg->struct_size != sizeof(dh_config))
-    return fail(DH_EINVAL, "Quasihole: dh_config.struct_size must equal sizeof(dh_config)");
-  if (q->struct_size != sizeof(dh_quasihole))
-    return fail(DH_EINVAL, "Quasihole: dh_quasihole.struct_size must equal sizeof(dh_quasihole) (" +
-                               std::to_string(sizeof(dh_quasihole)) + " bytes)");
-  if (cfg->network_type != DH_NETWORK_QUASIHOLE)
-    return fail(DH_EINVAL, "Quasihole: dh_create_quasihole needs network_type DH_NETWORK_QUASIHOLE");
-  return create_quasihole(cfg, q, out);
-}
-
-int dh_create_halperin(const dh_config* cfg, int m_up, int m_dn, int n_inter, dh_handle** out) {
-  if (!cfg || !out) return fail(DH_EINVAL, "Halperin: null argument");
-  if (cfg->struct_size != sizeof(dh_config))
-    return fail(DH_EINVAL, "Halperin: dh_config.struct_size must equal sizeof(dh_config)");
-  if (cfg->network_type != DH_NETWORK_HALPERIN)
-    return fail(DH_EINVAL, "Halperin: dh_create_halperin needs network_type DH_NETWORK_HALPERIN");
-  return create_halperin(cfg, m_up, m_dn, n_inter, out);
-}
-
-int dh_create_cf(const dh_config* cfg, const int* occ, int n_occ, dh_handle** out) {
-  if (!cfg || !out || !occ) return fail(DH_EINVAL, "null argument");
-  if (cfg->struct_size != sizeof(dh_config)) return fail(DH_EINVAL, "dh_config.struct_size must equal sizeof(dh_config)");
-  if (cfg->network_type != DH_NETWORK_JAIN) return fail(DH_EINVAL, "Jain: dh_create_cf needs network_type DH_NETWORK_JAIN");
-  return create_jain(cfg, occ, n_occ, out);
-}
 
 int dh_create(const dh_config* cfg, dh_handle** out) {
   if (!cfg || !out) return fail(DH_EINVAL, "null argument");
   if (cfg->struct_size != sizeof(dh_config))
     return fail(DH_EINVAL, "dh_config.struct_size must equal sizeof(dh_config) (" + std::to_string(sizeof(dh_config)) +
                                " bytes); the caller's binding has a different layout");
-  if (cfg->network_type == DH_NETWORK_LAUGHLIN) {
-    if (int rc = check_analytic(cfg, "Laughlin", 1)) return rc;
-    std::vector<int> ex;
-    if (int rc = laughlin_exponents(cfg, ex)) return rc;
-    *out = analytic_handle(cfg, dh_handle::LAUGHLIN, ex);
-    return DH_OK;
-  }
-  if (cfg->network_type == DH_NETWORK_JAIN) return create_jain(cfg, nullptr, 0, out);
-  if (cfg->network_type == DH_NETWORK_PFAFFIAN) return create_pfaffian(cfg, out);
-  if (cfg->network_type == DH_NETWORK_HALPERIN)
-    return fail(DH_EINVAL, "Halperin: the exponents (m_up, m_dn, n) are arguments of dh_create_halperin, not dh_create");
-  if (cfg->network_type == DH_NETWORK_QUASIHOLE)
-    return fail(DH_EINVAL, "Quasihole: the base and the holes are arguments of dh_create_quasihole, not dh_create");
-  if (cfg->network_type != DH_NETWORK_PSIFORMER) return fail(DH_EINVAL, "bad network type");
+  if (cfg->network_type != DH_NETWORK_PSIFORMER) return create_trial(cfg, out);  // api_trial.cpp
   const int N = cfg->n_up + cfg->n_dn;
   if (cfg->n_up < 0 || cfg->n_dn < 0 || N < 1 || N > 32) return fail(DH_EINVAL, "need 1 <= N <= 32 electrons");
   if (cfg->flux < 0 || cfg->flux > 126) return fail(DH_EINVAL, "need 0 <= flux <= 126");
@@ -503,7 +187,7 @@ void dh_destroy(dh_handle* h) {
   if (h->ref) (void)hipFree(h->ref);
   if (h->wb) (void)hipFree(h->wb);
   if (h->wbt) (void)hipFree(h->wbt);
-  if (h->expo) (void)hipFree(h->expo);
+  if (h->trial.table) (void)hipFree(h->trial.table);
   if (h->kfac) {
     if (h->kfac->dev_mem) (void)hipFree(h->kfac->dev_mem);
     delete h->kfac;
@@ -954,27 +638,6 @@ ChainDet chain_det(const dh_handle* h, const float* x, int nw, float* logpsi, co
   c.ldf = det_chain_ldf(d);
   c.epi = epi;
   return c;
-}
-
-// The kernel of an analytic state on nw walkers: log psi [nw][2] (e_l == nullptr), or the local
-// energy e_l [nw][2] and obs [nw][8].  Uploads the state's table at first use if it has one.
-int launch_trial(dh_handle* h, const float* x, float* logpsi, float* e_l, float* obs, int nw, hipStream_t s) {
-  if (!h->expo && !h->expo_host.empty()) {
-    HIP_TRY(hipMalloc(&h->expo, h->expo_host.size() * sizeof(int)));
-    HIP_TRY(hipMemcpy(h->expo, h->expo_host.data(), h->expo_host.size() * sizeof(int), hipMemcpyHostToDevice));
-  }
-  PROF(e_l ? PK_DET_ENERGY : PK_DET_VALUE, 0.0, e_l ? 48.0 * nw : 8.0 * nw * h->d.N);
-  if (h->state == dh_handle::QUASIHOLE)
-    launch_quasihole(h->d, x, h->quasihole, logpsi, e_l, obs, nw, s);
-  else if (h->state == dh_handle::HALPERIN)
-    launch_halperin(h->d, x, h->halperin[0], h->halperin[1], h->halperin[2], logpsi, e_l, obs, nw, s);
-  else if (h->state == dh_handle::PFAFFIAN)
-    launch_pfaffian(h->d, x, h->cfg.cf_flux, logpsi, e_l, obs, nw, s);
-  else if (h->state == dh_handle::JAIN)
-    launch_cf(h->d, x, h->expo, h->cf_dense, logpsi, e_l, obs, nw, s);
-  else
-    launch_laughlin(h->d, x, h->expo, logpsi, e_l, obs, nw, s);
-  return check_launch();
 }
 
 // log psi of nw walkers into logpsi [nw][2]: the Psiformer pass or an analytic state's kernel (launch_trial)

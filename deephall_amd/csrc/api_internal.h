@@ -1,5 +1,6 @@
 // What the host files of the C ABI share: api.cpp (create / destroy, parameters, the forward
-// Trunk, the value / MCMC / energy passes, debug hooks) and api_grad.cpp (the gradient side).
+// Trunk, the value / MCMC / energy passes, debug hooks), api_grad.cpp (the gradient side) and
+// api_trial.cpp (the parameter-free trial states).
 #pragma once
 #include <string>
 #include <vector>
@@ -105,15 +106,19 @@ struct dh_handle {
   bool params_set = false;
   bool ref_set = false;
   // Which wavefunction the handle is.  All but the Psiformer are analytic: no parameters, one
-  // kernel file each (laughlin.hip, cf.hip, pfaffian.hip, halperin.hip, quasihole.hip), launched by launch_trial
-  enum State { PSIFORMER, LAUGHLIN, JAIN, PFAFFIAN, HALPERIN, QUASIHOLE } state = PSIFORMER;
-  bool analytic() const { return state != PSIFORMER; }
-  int cf_dense = 0;               // Jain: the number of level-1 (dense) columns
-  int halperin[3] = {0, 0, 0};    // Halperin: m_up, m_dn, n (arguments of dh_create_halperin, not dh_config fields)
-  dh::QuasiholeState quasihole{};  // Quasihole: the base's weights and the holes (dh_create_quasihole)
-  std::vector<int> expo_host;     // Laughlin exponents [2][N] = (Q1 + m_j, Q1 - m_j); Jain: cf.hip's column table;
-                                  // Pfaffian, Halperin, Quasihole: empty
-  int* expo = nullptr;            // device copy (uploaded at first use)
+  // kernel file each (laughlin.hip, cf.hip, pfaffian.hip, halperin.hip, quasihole.hip), created
+  // and launched by api_trial.cpp, which alone reads what its state keeps here
+  enum State { PSIFORMER, LAUGHLIN, JAIN, PFAFFIAN, HALPERIN, QUASIHOLE };
+  struct Trial {
+    State state = PSIFORMER;
+    std::vector<int> table_host;     // Laughlin: the exponents [2][N] = (Q1 + m_j, Q1 - m_j) and the quasiparticle
+                                     // flag; Jain: cf.hip's column table; the other states: empty
+    int* table = nullptr;            // its device copy (uploaded at first use, freed by dh_destroy)
+    int cf_dense = 0;                // Jain: the number of level-1 (dense) columns
+    int halperin[3] = {0, 0, 0};     // Halperin: m_up, m_dn, n (arguments of dh_create_halperin, not dh_config fields)
+    dh::QuasiholeState quasihole{};  // Quasihole: the base's weights and the holes (dh_create_quasihole)
+  } trial;
+  bool analytic() const { return trial.state != PSIFORMER; }
   dh::KfacHost* kfac = nullptr;   // KFAC plan (built at first dh_kfac_* call)
   dh::Profiler prof;
 };
@@ -144,6 +149,19 @@ struct ProfScope {
   }
 };
 #define PROF(kind, flops, bytes) ProfScope prof_scope_##__LINE__(h, kind, (double)(flops), (double)(bytes), s)
+
+// The kernel classes of the profiler's records
+enum ProfKind { PK_GEMM = 0, PK_ATTN, PK_LN, PK_INPUT, PK_DET_VALUE, PK_DET_ENERGY, PK_MCMC, PK_COUNT };
+// channel-mode (C > 1) launches of GEMM/attention/LayerNorm/input are recorded as kind + PK_CH;
+// PK_L1CH: the local energy's layer 1 in one launch (gemm_lnch MODE 2)
+constexpr int PK_CH = PK_COUNT, PK_L1CH = PK_COUNT + 4, PK_TOTAL = PK_COUNT + 5;
+
+// api_trial.cpp.  create_trial: dh_create for every network type but the Psiformer (the handle
+// of an analytic state, or the refusal).  launch_trial: the kernel of an analytic state on nw
+// walkers, log psi [nw][2] (e_l == nullptr), or the local energy e_l [nw][2] and obs [nw][8];
+// uploads the state's table at first use if it has one.
+int create_trial(const dh_config* cfg, dh_handle** out);
+int launch_trial(dh_handle* h, const float* x, float* logpsi, float* e_l, float* obs, int nw, hipStream_t s);
 
 inline int check_common(dh_handle* h, const void* x, int B, void* ws, size_t ws_bytes, size_t need) {
   if (!h) return fail(DH_EINVAL, "null handle");

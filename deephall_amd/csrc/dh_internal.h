@@ -483,8 +483,8 @@ struct SparseBlocks {
 void launch_sparse_lll_grad(SparseBlocks blk, const float* dWfull, int ldw, const float* dbfull, int D, int NK, int M,
                             float* dWl, float* dbl, int acc, hipStream_t s);
 
-// The parameter-free trial states (their common device code: trial_common.h; api.cpp picks
-// the launcher in launch_trial).
+// The parameter-free trial states (their common device code: trial_common.h; api_trial.cpp
+// picks the launcher in launch_trial).
 // laughlin.hip: log psi (e_l == nullptr) or the local energy (e_l [nw][2], obs [nw][8])
 // of the Laughlin wavefunction; expo [2][N] = (Q1 + m_j, Q1 - m_j)
 size_t laughlin_smem_bytes(int N);

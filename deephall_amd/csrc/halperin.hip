@@ -35,12 +35,6 @@ namespace {
 
 constexpr int kValueNT = 256;  // threads of a value workgroup
 
-// c_ik of the species blocks
-__device__ __forceinline__ double halperin_weight(int i, int k, int n_up, int m_up, int m_dn, int n_int) {
-  const bool iu = i < n_up, ku = k < n_up;
-  return (double)(iu != ku ? n_int : iu ? m_up : m_dn);
-}
-
 // sum_{i<k} c_ik log w_ik of one walker by the G lanes of its group (lane = index in the group;
 // a lane with live == false adds nothing but takes part in the shuffles); every lane of the
 // group gets the sum.  UV: SU entries per electron, u and v first.  Every product and sum is
@@ -53,7 +47,7 @@ __device__ __forceinline__ zd halperin_logpsi(const zd* UV, int SU, int N, int n
   for (int q = live ? lane : N * N; q < N * N; q += G) {
     const int i = q / N, k = q % N;
     if (k <= i) continue;
-    const double c = halperin_weight(i, k, n_up, m_up, m_dn, n_int);
+    const double c = species_weight(i, k, n_up, m_up, m_dn, n_int);
     if (c == 0.0) continue;
     const zd ui = UV[SU * i], vi = UV[SU * i + 1], uk = UV[SU * k], vk = UV[SU * k + 1];
     const double a_re = ui.re * vk.re, a_re2 = ui.im * vk.im, b_re = uk.re * vi.re, b_re2 = uk.im * vi.im;
@@ -135,7 +129,7 @@ __global__ __launch_bounds__(64) void halperin_energy_kernel(const float* __rest
   // gradient: g_a = sum_k c d log w, the up partners then the down partners
   for (int a = tid; a < T; a += nt) {
     const int e = a >> 1, c = a & 1;
-    const double wu = halperin_weight(e, 0, n_up, m_up, m_dn, n_int), wd = halperin_weight(e, N - 1, n_up, m_up, m_dn, n_int);
+    const double wu = species_weight(e, 0, n_up, m_up, m_dn, n_int), wd = species_weight(e, N - 1, n_up, m_up, m_dn, n_int);
     zd s{0.0, 0.0};
     if (n_up > 0 && wu != 0.0) s = pair_grad(s, UV, n_up, e, c, wu);
     if (n_dn > 0 && wd != 0.0) s = pair_grad(s, UV + 12 * n_up, n_dn, e - n_up, c, wd);
@@ -146,11 +140,11 @@ __global__ __launch_bounds__(64) void halperin_energy_kernel(const float* __rest
     const int a = idx / T, bb = idx % T, ea = a >> 1, ca = a & 1, eb = bb >> 1, cb = bb & 1;
     zd h{0.0, 0.0};
     if (ea == eb) {
-      const double wu = halperin_weight(ea, 0, n_up, m_up, m_dn, n_int), wd = halperin_weight(ea, N - 1, n_up, m_up, m_dn, n_int);
+      const double wu = species_weight(ea, 0, n_up, m_up, m_dn, n_int), wd = species_weight(ea, N - 1, n_up, m_up, m_dn, n_int);
       if (n_up > 0 && wu != 0.0) h = pair_hess_same(h, UV, n_up, ea, ca, cb, wu);
       if (n_dn > 0 && wd != 0.0) h = pair_hess_same(h, UV + 12 * n_up, n_dn, ea - n_up, ca, cb, wd);
     } else {
-      const double w = halperin_weight(ea, eb, n_up, m_up, m_dn, n_int);
+      const double w = species_weight(ea, eb, n_up, m_up, m_dn, n_int);
       if (w != 0.0) h = pair_hess_cross(h, UV + 12 * ea, UV + 12 * eb, ca, cb, w);
     }
     H[idx] = h;

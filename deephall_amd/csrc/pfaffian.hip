@@ -3,19 +3,11 @@
 //   log psi = log Pf(A) + 2 p sum_{i<k} log w_ik,  A_ik = 1 / w_ik (i != k), A_ii = 0,
 //   w_ik = u_i v_k - u_k v_i,  u = cos(theta/2) e^(i phi/2),  v = sin(theta/2) e^(-i phi/2)
 //
-// at flux 2Q = 2 p (N - 1) - 1, N even.  Pf(A) comes from a skew-symmetric elimination with
-// pivoting (Parlett-Reid in 2x2 blocks): at step k = 0, 2, ... the largest |A[k][j]|, j > k, is
-// brought to column k + 1 by swapping row and column j with k + 1 (a factor -1), the pivot
-// P = A[k][k+1] is multiplied into Pf, and the trailing block takes the rank-2 skew update
-//   A[i][j] += (A[i][k] A[k+1][j] - A[i][k+1] A[k][j]) / P,   i, j >= k + 2,
-// which is the row operation row_i += (A[i][k] / P) row_{k+1} - (A[i][k+1] / P) row_k alone: the
-// matching column operation only clears rows k, k + 1, which are not read again.  The value-only
-// instantiation (dh_logpsi, dh_mcmc_step) keeps u, v and A and does this in place.
-//
-// The energy instantiation applies the same row operations and swaps to [A | I]; the right
-// half becomes M with M A M^T = D, D the block diagonal of the pivots, and
-//   W = A^-1 = M^T D^-1 M,   W[i][j] = sum_k (M[k+1][i] M[k][j] - M[k][i] M[k+1][j]) / P_k.
-// The left half and so the pivots are those of the value instantiation.  With n(a) the electron
+// at flux 2Q = 2 p (N - 1) - 1, N even.  Pf(A) comes from trial_common.h's skew_eliminate (the
+// algorithm is explained there): in place on A for the value-only instantiation (dh_logpsi,
+// dh_mcmc_step), on [A | I] for the energy, whose right half becomes M with M A M^T = D, D the
+// block diagonal of the pivots, and W = A^-1 = M^T D^-1 M (pfaffian_inverse).  The left half
+// and so the pivots are those of the value instantiation.  With n(a) the electron
 // of coordinate a, d_a[k] = d(1 / w_{n(a) k}) / dx_a (dA_a = e_n d_a^T - d_a e_n^T), y_a = W d_a:
 //   d_a log Pf     = sum_k W[k][n(a)] d_a[k] = -y_a[n(a)]
 //   d_a d_b log Pf = 1/2 tr(W d2A_ab) - y_a[n(b)] y_b[n(a)] + (d_a . y_b) W[n(b)][n(a)]
@@ -94,56 +86,8 @@ __global__ __launch_bounds__(64) void pfaffian_kernel(const float* __restrict__ 
     }
   }
   __syncthreads();
-  // skew elimination with pivoting (|re| + |im| pivot, as det.hip) on [A | I], or on A alone for
-  // the value: the left block and so the pivots are the same
-  for (int k = 0; k < N; k += 2) {
-    if (tid == 0) {
-      double best = -1.0;
-      int bj = k + 1;
-      for (int j = k + 1; j < N; ++j) {
-        const double v = fabs(G[k * ld + j].re) + fabs(G[k * ld + j].im);
-        if (v > best) {
-          best = v;
-          bj = j;
-        }
-      }
-      *pivd = (double)bj;
-    }
-    __syncthreads();
-    const int pc = (int)*pivd;
-    if (pc != k + 1) {  // rows, then columns (of the left block)
-      for (int c = tid; c < ld; c += nt) {
-        const zd t = G[(k + 1) * ld + c];
-        G[(k + 1) * ld + c] = G[pc * ld + c];
-        G[pc * ld + c] = t;
-      }
-      __syncthreads();
-      for (int r = tid; r < N; r += nt) {
-        const zd t = G[r * ld + k + 1];
-        G[r * ld + k + 1] = G[r * ld + pc];
-        G[r * ld + pc] = t;
-      }
-      __syncthreads();
-    }
-    const zd P = G[k * ld + k + 1];
-    const zd Pinv = zinv(P);
-    if (tid == 0) {
-      logpf->re += 0.5 * log(P.re * P.re + P.im * P.im);
-      logpf->im += atan2(P.im, P.re) + (pc != k + 1 ? M_PI : 0.0);
-      if (ENERGY) pinv[k >> 1] = Pinv;
-    }
-    for (int r = k + 2 + tid; r < N; r += nt) {
-      f0[r] = G[r * ld + k] * Pinv;
-      f1[r] = G[r * ld + k + 1] * Pinv;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < N * ld; idx += nt) {
-      const int r = idx / ld, c = idx % ld;
-      if (r < k + 2 || c < k + 2) continue;
-      G[r * ld + c] = G[r * ld + c] + f0[r] * G[(k + 1) * ld + c] - f1[r] * G[k * ld + c];
-    }
-    __syncthreads();
-  }
+  // on [A | I], or on A alone for the value: the left block and so the pivots are the same
+  skew_eliminate<ENERGY>(G, N, ld, f0, f1, pinv, logpf, pivd, tid, nt);
   // pair part of log psi (value): 2 p sum_{i<j} log w_ij
   const zd lpair = pair_logpsi(UV, SU, N, p2, false, tid, nt);
   if (!ENERGY) {
@@ -154,25 +98,8 @@ __global__ __launch_bounds__(64) void pfaffian_kernel(const float* __restrict__ 
     return;
   }
   zd *W = sm + L.W, *d = sm + L.d, *Y = sm + L.y, *g = sm + L.g, *H = sm + L.H;
-  // W = M^T D^-1 M
-  for (int idx = tid; idx < NN; idx += nt) {
-    const int i = idx / N, j = idx % N;
-    zd s{0.0, 0.0};
-    for (int k = 0; k < N; k += 2) {
-      const zd *m0 = G + k * ld + N, *m1 = m0 + ld;
-      s = s + (m1[i] * m0[j] - m0[i] * m1[j]) * pinv[k >> 1];
-    }
-    W[idx] = s;
-  }
-  __syncthreads();
-  // y[a][j] = (W d_a)[j],  a = 2 e + (0 theta | 1 phi)
-  for (int idx = tid; idx < T * N; idx += nt) {
-    const int a = idx / N, j = idx % N;
-    zd s{0.0, 0.0};
-    for (int k = 0; k < N; ++k) s = s + W[j * N + k] * d[a * N + k];
-    Y[idx] = s;
-  }
-  __syncthreads();
+  // W = M^T D^-1 M and y[a][j] = (W d_a)[j],  a = 2 e + (0 theta | 1 phi)
+  pfaffian_inverse(G, N, pinv, d, W, Y, tid, nt);
   // gradient: Pfaffian + pairs
   for (int a = tid; a < T; a += nt) {
     const int e = a >> 1, c = a & 1;

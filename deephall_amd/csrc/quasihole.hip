@@ -6,7 +6,7 @@
 // is w of electron i and the hole: zero with the electron on the hole.
 //
 //   Halperin base: log psi = sum_{i<k} c_ik log w_ik + sum_a sum_{i in S_a} log s_a(i)
-//     c_ik as in halperin.hip; S_a all electrons, the up slots or the down slots by the hole's kind.
+//     c_ik = species_weight; S_a all electrons, the up slots or the down slots by the hole's kind.
 //   Pfaffian base: the 2 k holes of the groups A and B, and Abelian holes acting on every electron,
 //     F_i = prod_{a in A} s_a(i),  G_i = prod_{b in B} s_b(i),
 //     A_ik = (F_i G_k + F_k G_i) / w_ik (i != k),  A_ii = 0,
@@ -15,7 +15,7 @@
 //
 // No normalisation; Im log psi is the principal phase.  Both bases are the pair part of
 // halperin.hip (the Pfaffian base with all three weights 2 p), a one-body part, and for the
-// Pfaffian base the skew elimination of pfaffian.hip on the new A.
+// Pfaffian base the skew elimination pfaffian.hip uses (skew_eliminate) on the new A.
 //
 // One-body part: with s_x = du_x V - dv_x U and s_xy = d2u_xy V - d2v_xy U it adds log s to
 // log psi, s_x / s to g[2 i + c] and s_xy / s - s_x s_y / s^2 to the same-electron Hessian block,
@@ -84,12 +84,6 @@ __host__ __device__ inline QSm qsm_layout(int N, bool pf, bool energy) {
   return L;
 }
 
-// c_ik of the species blocks (halperin.hip)
-__device__ __forceinline__ double pair_weight(int i, int k, int n_up, int m_up, int m_dn, int n_int) {
-  const bool iu = i < n_up, ku = k < n_up;
-  return (double)(iu != ku ? n_int : iu ? m_up : m_dn);
-}
-
 // does a hole of this kind act on electron i through the one-body part?
 __device__ __forceinline__ bool hole_acts(int kind, int i, int n_up) {
   return kind == DH_HOLE_BOTH || (kind == DH_HOLE_UP && i < n_up) || (kind == DH_HOLE_DOWN && i >= n_up);
@@ -101,7 +95,7 @@ __device__ __forceinline__ zd pair_log(const zd* UV, int SU, int N, int n_up, in
   for (int q = tid; q < N * N; q += 64) {
     const int i = q / N, k = q % N;
     if (k <= i) continue;
-    const double c = pair_weight(i, k, n_up, m_up, m_dn, n_int);
+    const double c = species_weight(i, k, n_up, m_up, m_dn, n_int);
     if (c == 0.0) continue;  // an up and a down electron may coincide at n = 0
     const zd w = UV[SU * i] * UV[SU * k + 1] - UV[SU * k] * UV[SU * i + 1];
     lre += (0.5 * c) * log(w.re * w.re + w.im * w.im);
@@ -250,56 +244,9 @@ __global__ __launch_bounds__(64) void quasihole_kernel(const float* __restrict__
       }
     }
     __syncthreads();
-    // skew elimination with pivoting on [A | I], or on A alone for the value, as pfaffian.hip:
-    // the left block and so the pivots are the same
-    for (int k = 0; k < N; k += 2) {
-      if (tid == 0) {
-        double best = -1.0;
-        int bj = k + 1;
-        for (int j = k + 1; j < N; ++j) {
-          const double v = fabs(G[k * ld + j].re) + fabs(G[k * ld + j].im);
-          if (v > best) {
-            best = v;
-            bj = j;
-          }
-        }
-        *pivd = (double)bj;
-      }
-      __syncthreads();
-      const int pc = (int)*pivd;
-      if (pc != k + 1) {  // rows, then columns (of the left block)
-        for (int c = tid; c < ld; c += nt) {
-          const zd t = G[(k + 1) * ld + c];
-          G[(k + 1) * ld + c] = G[pc * ld + c];
-          G[pc * ld + c] = t;
-        }
-        __syncthreads();
-        for (int r = tid; r < N; r += nt) {
-          const zd t = G[r * ld + k + 1];
-          G[r * ld + k + 1] = G[r * ld + pc];
-          G[r * ld + pc] = t;
-        }
-        __syncthreads();
-      }
-      const zd P = G[k * ld + k + 1];
-      const zd Pinv = zinv(P);
-      if (tid == 0) {
-        logpf->re += 0.5 * log(P.re * P.re + P.im * P.im);
-        logpf->im += atan2(P.im, P.re) + (pc != k + 1 ? M_PI : 0.0);
-        if (ENERGY) pinv[k >> 1] = Pinv;
-      }
-      for (int r = k + 2 + tid; r < N; r += nt) {
-        f0[r] = G[r * ld + k] * Pinv;
-        f1[r] = G[r * ld + k + 1] * Pinv;
-      }
-      __syncthreads();
-      for (int idx = tid; idx < N * ld; idx += nt) {
-        const int r = idx / ld, c = idx % ld;
-        if (r < k + 2 || c < k + 2) continue;
-        G[r * ld + c] = G[r * ld + c] + f0[r] * G[(k + 1) * ld + c] - f1[r] * G[k * ld + c];
-      }
-      __syncthreads();
-    }
+    // on [A | I], or on A alone for the value, as pfaffian.hip: the left block and so the pivots
+    // are the same
+    skew_eliminate<ENERGY>(G, N, ld, f0, f1, pinv, logpf, pivd, tid, nt);
   }
   // pair and one-body parts of log psi
   const zd lrest = pair_log(UV, SU, N, n_up, m_up, m_dn, n_int, tid) + hole_log(UV, SU, N, n_up, HU, kind, nh, tid);
@@ -312,33 +259,12 @@ __global__ __launch_bounds__(64) void quasihole_kernel(const float* __restrict__
   }
   zd *g = sm + L.g, *H = sm + L.H;
   zd *FG = sm + L.fg, *W = sm + L.W, *d = sm + L.d, *Y = sm + L.y;  // Pfaffian base only
-  if (PF) {
-    const zd *G = sm + L.G, *pinv = sm + L.misc + 2 * N;
-    const int ld = 2 * N;
-    // W = M^T D^-1 M
-    for (int idx = tid; idx < NN; idx += nt) {
-      const int i = idx / N, j = idx % N;
-      zd s{0.0, 0.0};
-      for (int k = 0; k < N; k += 2) {
-        const zd *m0 = G + k * ld + N, *m1 = m0 + ld;
-        s = s + (m1[i] * m0[j] - m0[i] * m1[j]) * pinv[k >> 1];
-      }
-      W[idx] = s;
-    }
-    __syncthreads();
-    // y[a][j] = (W d_a)[j],  a = 2 e + (0 theta | 1 phi)
-    for (int idx = tid; idx < T * N; idx += nt) {
-      const int a = idx / N, j = idx % N;
-      zd s{0.0, 0.0};
-      for (int k = 0; k < N; ++k) s = s + W[j * N + k] * d[a * N + k];
-      Y[idx] = s;
-    }
-    __syncthreads();
-  }
+  // W = M^T D^-1 M and y[a][j] = (W d_a)[j],  a = 2 e + (0 theta | 1 phi)
+  if (PF) pfaffian_inverse(sm + L.G, N, sm + L.misc + 2 * N /* 1 / pivot */, d, W, Y, tid, nt);
   // gradient: Pfaffian, then pairs (the up partners, the down partners), then holes
   for (int a = tid; a < T; a += nt) {
     const int e = a >> 1, c = a & 1;
-    const double wu = pair_weight(e, 0, n_up, m_up, m_dn, n_int), wd = pair_weight(e, N - 1, n_up, m_up, m_dn, n_int);
+    const double wu = species_weight(e, 0, n_up, m_up, m_dn, n_int), wd = species_weight(e, N - 1, n_up, m_up, m_dn, n_int);
     zd s{0.0, 0.0};
     if (PF) s = s - Y[a * N + e];
     if (n_up > 0 && wu != 0.0) s = pair_grad(s, UV, n_up, e, c, wu);
@@ -352,7 +278,7 @@ __global__ __launch_bounds__(64) void quasihole_kernel(const float* __restrict__
     zd h{0.0, 0.0};
     if (PF) h = h - Y[a * N + eb] * Y[bb * N + ea];
     if (ea == eb) {
-      const double wu = pair_weight(ea, 0, n_up, m_up, m_dn, n_int), wd = pair_weight(ea, N - 1, n_up, m_up, m_dn, n_int);
+      const double wu = species_weight(ea, 0, n_up, m_up, m_dn, n_int), wd = species_weight(ea, N - 1, n_up, m_up, m_dn, n_int);
       if (n_up > 0 && wu != 0.0) h = pair_hess_same(h, UV, n_up, ea, ca, cb, wu);
       if (n_dn > 0 && wd != 0.0) h = pair_hess_same(h, UV + 12 * n_up, n_dn, ea - n_up, ca, cb, wd);
       h = hole_hess(h, qa, ea, ca, cb, n_up, HU, kind, nh);
@@ -373,7 +299,7 @@ __global__ __launch_bounds__(64) void quasihole_kernel(const float* __restrict__
         }
       }
     } else {
-      const double w = pair_weight(ea, eb, n_up, m_up, m_dn, n_int);
+      const double w = species_weight(ea, eb, n_up, m_up, m_dn, n_int);
       if (w != 0.0) h = pair_hess_cross(h, qa, qb, ca, cb, w);
       if (PF) {  // x = coordinate ca of electron ea, y = coordinate cb of electron eb
         const zd *Fa = FG + 12 * ea, *Fb = FG + 12 * eb;

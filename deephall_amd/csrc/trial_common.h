@@ -1,11 +1,15 @@
-// Device code shared by the parameter-free trial states (laughlin.hip, cf.hip, pfaffian.hip):
-// complex double, the spinor coordinates u, v and their derivatives, the monomial u^a v^b, the
-// pair quotient of the LLL-projected second-level orbitals, the Gauss-Jordan elimination, the
-// pair (Jastrow) part of log psi with its gradient and Hessian, and the kinetic / angular
-// momentum / potential assembly from the gradient g and the full Hessian H of log psi.
+// Device code shared by the parameter-free trial states (laughlin.hip, cf.hip, pfaffian.hip,
+// halperin.hip, quasihole.hip): complex double, the spinor coordinates u, v and their
+// derivatives, the monomial u^a v^b, the pair quotient of the LLL-projected second-level
+// orbitals, the Gauss-Jordan elimination, the skew (Pfaffian) elimination and the inverse it
+// gives, the species weights of a two-component state, the pair (Jastrow) part of log psi with
+// its gradient and Hessian, and the kinetic / angular momentum / potential assembly from the
+// gradient g and the full Hessian H of log psi.
 //
-// Each kernel is one 64-thread workgroup per walker with everything in LDS; (tid, nt) are its
-// thread index and count.  The helpers that replace what used to be inline kernel code are
+// Each kernel is one 64-thread workgroup per walker with everything in LDS (halperin.hip's value
+// kernel apart: several walkers per workgroup); (tid, nt) are its thread index and count.  A
+// helper is compiled with the flags of the file that includes it: quasihole.hip's copy is
+// uncontracted, pfaffian.hip's is not.  The helpers that replace what used to be inline kernel code are
 // __forceinline__ and take their accumulator by value, so that every kernel keeps the
 // expression tree (summation order, fused multiply-adds) it had with the code written out.
 #pragma once
@@ -191,6 +195,107 @@ __device__ __forceinline__ void gauss_jordan(zd* E, int N, int ld, zd* fac, zd* 
     }
     __syncthreads();
   }
+}
+
+// Pf(A) of a skew-symmetric A by elimination with pivoting (Parlett-Reid in 2x2 blocks): at step
+// k = 0, 2, ... the largest |A[k][j]|, j > k (|re| + |im|, as det.hip), is brought to column k + 1
+// by swapping row and column j with k + 1 (a factor -1), the pivot P = A[k][k+1] is multiplied
+// into Pf, and the trailing block takes the rank-2 skew update
+//   A[i][j] += (A[i][k] A[k+1][j] - A[i][k+1] A[k][j]) / P,   i, j >= k + 2,
+// which is the row operation row_i += (A[i][k] / P) row_{k+1} - (A[i][k+1] / P) row_k alone: the
+// matching column operation only clears rows k, k + 1, which are not read again.
+//
+// On the N rows of G (leading dimension ld: N for A alone, in place; 2 N for [A | I], to which
+// the same row operations and swaps are applied: the right half becomes M with M A M^T = D, D the
+// block diagonal of the pivots; the left block and so the pivots are the same).  In LDS, the
+// caller's: f0, f1, the factor columns [N]; pinv (ENERGY only), 1 / pivot of step k at [k / 2];
+// logpf (zeroed by the caller and G complete before its last barrier; log Pf after the call);
+// pivd, the pivot column of the current step (an int in a double is exact).
+template <bool ENERGY>
+__device__ __forceinline__ void skew_eliminate(zd* G, int N, int ld, zd* f0, zd* f1, zd* pinv, zd* logpf, double* pivd,
+                                               int tid, int nt) {
+  for (int k = 0; k < N; k += 2) {
+    if (tid == 0) {
+      double best = -1.0;
+      int bj = k + 1;
+      for (int j = k + 1; j < N; ++j) {
+        const double v = fabs(G[k * ld + j].re) + fabs(G[k * ld + j].im);
+        if (v > best) {
+          best = v;
+          bj = j;
+        }
+      }
+      *pivd = (double)bj;
+    }
+    __syncthreads();
+    const int pc = (int)*pivd;
+    if (pc != k + 1) {  // rows, then columns (of the left block)
+      for (int c = tid; c < ld; c += nt) {
+        const zd t = G[(k + 1) * ld + c];
+        G[(k + 1) * ld + c] = G[pc * ld + c];
+        G[pc * ld + c] = t;
+      }
+      __syncthreads();
+      for (int r = tid; r < N; r += nt) {
+        const zd t = G[r * ld + k + 1];
+        G[r * ld + k + 1] = G[r * ld + pc];
+        G[r * ld + pc] = t;
+      }
+      __syncthreads();
+    }
+    const zd P = G[k * ld + k + 1];
+    const zd Pinv = zinv(P);
+    if (tid == 0) {
+      logpf->re += 0.5 * log(P.re * P.re + P.im * P.im);
+      logpf->im += atan2(P.im, P.re) + (pc != k + 1 ? M_PI : 0.0);
+      if (ENERGY) pinv[k >> 1] = Pinv;
+    }
+    for (int r = k + 2 + tid; r < N; r += nt) {
+      f0[r] = G[r * ld + k] * Pinv;
+      f1[r] = G[r * ld + k + 1] * Pinv;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < N * ld; idx += nt) {
+      const int r = idx / ld, c = idx % ld;
+      if (r < k + 2 || c < k + 2) continue;
+      G[r * ld + c] = G[r * ld + c] + f0[r] * G[(k + 1) * ld + c] - f1[r] * G[k * ld + c];
+    }
+    __syncthreads();
+  }
+}
+
+// The inverse behind the derivatives of log Pf, from [A | I] as skew_eliminate<true> leaves it
+// (G, leading dimension 2 N, and pinv, complete before the call):
+//   W = A^-1 = M^T D^-1 M,   W[i][j] = sum_k (M[k+1][i] M[k][j] - M[k][i] M[k+1][j]) / P_k,
+// then Y[a][j] = (W d_a)[j] for the 2 N rows d_a [N] of d, a = 2 e + (0 theta | 1 phi), also
+// complete before the call.  W [N][N] and Y [2 N][N] are the caller's LDS, complete after it.
+__device__ __forceinline__ void pfaffian_inverse(const zd* G, int N, const zd* pinv, const zd* d, zd* W, zd* Y, int tid,
+                                                 int nt) {
+  const int ld = 2 * N;
+  for (int idx = tid; idx < N * N; idx += nt) {
+    const int i = idx / N, j = idx % N;
+    zd s{0.0, 0.0};
+    for (int k = 0; k < N; k += 2) {
+      const zd *m0 = G + k * ld + N, *m1 = m0 + ld;
+      s = s + (m1[i] * m0[j] - m0[i] * m1[j]) * pinv[k >> 1];
+    }
+    W[idx] = s;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < 2 * N * N; idx += nt) {
+    const int a = idx / N, j = idx % N;
+    zd s{0.0, 0.0};
+    for (int k = 0; k < N; ++k) s = s + W[j * N + k] * d[a * N + k];
+    Y[idx] = s;
+  }
+  __syncthreads();
+}
+
+// Weight c_ik of the pair (i, k) of a two-species state, the slots below n_up up and the rest
+// down: m_up (both up), m_dn (both down), n_int (one of each)
+__device__ __forceinline__ double species_weight(int i, int k, int n_up, int m_up, int m_dn, int n_int) {
+  const bool iu = i < n_up, ku = k < n_up;
+  return (double)(iu != ku ? n_int : iu ? m_up : m_dn);
 }
 
 // Pair part of log psi, weight sum_{i<j} log w_ij with w_ij = u_i v_j - u_j v_i, summed over

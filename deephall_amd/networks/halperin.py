@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import torch
 
-from .laughlin import Laughlin, analytic_spec
+from .laughlin import Laughlin, TrialCallable
 
 
 def check_halperin(nspins, flux, exponents) -> tuple:
@@ -54,23 +54,17 @@ def check_halperin(nspins, flux, exponents) -> tuple:
 class Halperin(Laughlin):
     """Parameter-free analytic wavefunction on halperin.hip."""
 
+    name = "Halperin"
+    network_type = "halperin"
+
     def __init__(self, nspins, flux, exponents=(3, 3, 2), system=None):
-        self.nspins = tuple(int(n) for n in nspins)
-        self.flux = int(flux)
+        self._sphere(nspins, flux)
         self.exponents = check_halperin(self.nspins, self.flux, exponents)
-        self.Q = self.flux / 2
-        self.spec = analytic_spec(system, nspins=self.nspins, flux=self.flux, network_type="halperin",
-                                  halperin=self.exponents)
-        self._flat_cache = {}
-        self._epoch = 0
-
-    def vjp(self, *args, **kwargs):
-        raise TypeError("the Halperin wavefunction has no parameters to differentiate")
+        self.spec = self._spec(system, halperin=self.exponents)
 
 
-class HalperinCallable:
-    """log psi of walkers x [N, 2] (per walker, the reference's f convention) or data
-    [B, N, 2] (batched), complex128.  No parameters."""
+class HalperinCallable(TrialCallable):
+    """`Halperin` in torch operations (see `TrialCallable`)."""
 
     def __init__(self, nspins, flux, exponents=(3, 3, 2), system=None):
         self.nspins = tuple(int(n) for n in nspins)
@@ -83,9 +77,6 @@ class HalperinCallable:
         c = torch.where(up[:, None] & up[None, :], m_up, torch.where(~up[:, None] & ~up[None, :], m_dn, n))
         self._c = torch.triu(c, diagonal=1).to(torch.float64)  # c_ik for i < k, 0 elsewhere
 
-    def init(self, key=None, data=None, device=None) -> dict:
-        return {}
-
     def _logpsi(self, x: torch.Tensor) -> torch.Tensor:
         x = x.to(torch.float64)
         theta, phi = x[:, 0], x[:, 1]
@@ -97,13 +88,6 @@ class HalperinCallable:
         # coincide) is taken out before the logarithm: 0 x log 0 must not reach the sum
         w = torch.where(c != 0, w, torch.ones_like(w))
         return torch.sum(c * torch.log(w))
-
-    def __call__(self, params, data: torch.Tensor) -> torch.Tensor:
-        if data.dim() == 2:
-            return self._logpsi(data)
-        return torch.vmap(self._logpsi)(data)
-
-    apply = __call__
 
 
 __all__ = ["Halperin", "HalperinCallable", "check_halperin"]

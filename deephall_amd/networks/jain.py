@@ -26,7 +26,7 @@ from __future__ import annotations
 
 import torch
 
-from .laughlin import Laughlin, analytic_spec, laughlin_q1
+from .laughlin import Laughlin, TrialCallable, laughlin_q1
 
 
 def default_occupation(nspins, flux, cf_flux: int = 1) -> tuple:
@@ -64,11 +64,12 @@ def check_occupation(nspins, flux, cf_flux, occupation) -> tuple:
 class Jain(Laughlin):
     """Parameter-free analytic wavefunction on cf.hip."""
 
+    name = "Jain"
+    network_type = "jain"
+
     def __init__(self, nspins, flux, cf_flux: int = 1, occupation=None, system=None):
-        self.nspins = tuple(int(n) for n in nspins)
-        self.flux = int(flux)
+        self._sphere(nspins, flux)
         self.cf_flux = int(cf_flux)
-        self.Q = self.flux / 2
         self.Q1 = laughlin_q1(self.nspins, self.flux, self.cf_flux)
         if occupation is None:
             self.occupation = default_occupation(self.nspins, self.flux, self.cf_flux)
@@ -76,18 +77,11 @@ class Jain(Laughlin):
         else:
             occ2 = check_occupation(self.nspins, self.flux, self.cf_flux, occupation)
             self.occupation = tuple((n, m2 / 2) for n, m2 in occ2)
-        self.spec = analytic_spec(system, nspins=self.nspins, flux=self.flux, network_type="jain",
-                                  cf_flux=self.cf_flux, occupation=occ2)
-        self._flat_cache = {}
-        self._epoch = 0
-
-    def vjp(self, *args, **kwargs):
-        raise TypeError("the Jain wavefunction has no parameters to differentiate")
+        self.spec = self._spec(system, cf_flux=self.cf_flux, occupation=occ2)
 
 
-class JainCallable:
-    """log psi of walkers x [N, 2] (per walker, the reference's f convention) or data
-    [B, N, 2] (batched), complex128.  No parameters."""
+class JainCallable(TrialCallable):
+    """`Jain` through ``slogdet`` (see `TrialCallable`)."""
 
     def __init__(self, nspins, flux, cf_flux: int = 1, occupation=None, system=None):
         self.nspins = tuple(int(n) for n in nspins)
@@ -101,9 +95,6 @@ class JainCallable:
         self.occupation = tuple((n, m2 / 2) for n, m2 in occ2)
         q2 = int(round(2 * self.Q1))
         self._cols = tuple((n, (q2 + m2) // 2, (q2 - m2) // 2) for n, m2 in occ2)  # (n, A, B)
-
-    def init(self, key=None, data=None, device=None) -> dict:
-        return {}
 
     def _logpsi(self, x: torch.Tensor) -> torch.Tensor:
         x = x.to(torch.float64)
@@ -131,13 +122,6 @@ class JainCallable:
         sign, logdet = torch.linalg.slogdet(torch.stack(cols, dim=-1))
         pair = torch.sum(torch.triu(torch.log(w), diagonal=1))  # sum_{i<k} log w_ik
         return logdet + torch.log(sign) + 2 * p * pair
-
-    def __call__(self, params, data: torch.Tensor) -> torch.Tensor:
-        if data.dim() == 2:
-            return self._logpsi(data)
-        return torch.vmap(self._logpsi)(data)
-
-    apply = __call__
 
 
 __all__ = ["Jain", "JainCallable", "default_occupation", "check_occupation"]

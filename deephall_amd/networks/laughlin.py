@@ -38,18 +38,28 @@ def analytic_spec(system, **fields) -> NetworkSpec:
 
 
 class Laughlin(Psiformer):
-    """Parameter-free analytic wavefunction sharing the Psiformer's native plumbing."""
+    """Parameter-free analytic wavefunction sharing the Psiformer's native plumbing, and the base of
+    the other native trial states: a subclass names itself and its network type, calls `_sphere`
+    first and sets ``spec`` from `_spec` with its own fields once it has checked them."""
+
+    name = "Laughlin"  # in the refusal of `vjp`
+    network_type = "laughlin"
 
     def __init__(self, nspins, flux, cf_flux: int = 1, excitation_lz: float = 0.0, system=None):
-        self.nspins = tuple(int(n) for n in nspins)
-        self.flux = int(flux)
+        self._sphere(nspins, flux)
         self.cf_flux = int(cf_flux)
         self.excitation_lz = float(excitation_lz)
+        self.spec = self._spec(system, excitation_lz=self.excitation_lz, cf_flux=self.cf_flux)
+
+    def _sphere(self, nspins, flux):
+        self.nspins = tuple(int(n) for n in nspins)
+        self.flux = int(flux)
         self.Q = self.flux / 2
-        self.spec = analytic_spec(system, nspins=self.nspins, flux=self.flux, network_type="laughlin",
-                                  excitation_lz=self.excitation_lz, cf_flux=self.cf_flux)
         self._flat_cache = {}
         self._epoch = 0
+
+    def _spec(self, system, **fields) -> NetworkSpec:
+        return analytic_spec(system, nspins=self.nspins, flux=self.flux, network_type=self.network_type, **fields)
 
     def init(self, key=None, data=None, device=None) -> ParamTree:
         if device is None:
@@ -60,7 +70,23 @@ class Laughlin(Psiformer):
         return get_handle(self.spec, device)  # nothing to upload
 
     def vjp(self, *args, **kwargs):
-        raise TypeError("the Laughlin wavefunction has no parameters to differentiate")
+        raise TypeError(f"the {self.name} wavefunction has no parameters to differentiate")
+
+
+class TrialCallable:
+    """A trial state as a torch log-psi callable: log psi of walkers x [N, 2] (per walker, the
+    reference's f convention) or data [B, N, 2] (batched), complex128.  No parameters.  A subclass
+    checks its arguments in its constructor and has ``_logpsi`` of one walker."""
+
+    def init(self, key=None, data=None, device=None) -> dict:
+        return {}
+
+    def __call__(self, params, data: torch.Tensor) -> torch.Tensor:
+        if data.dim() == 2:
+            return self._logpsi(data)
+        return torch.vmap(self._logpsi)(data)
+
+    apply = __call__
 
 
 def laughlin_q1(nspins, flux, cf_flux: int = 1) -> float:
@@ -68,7 +94,7 @@ def laughlin_q1(nspins, flux, cf_flux: int = 1) -> float:
     return float(flux) / 2 - int(cf_flux) * (sum(nspins) - 1)
 
 
-class LaughlinQuasiparticle:
+class LaughlinQuasiparticle(TrialCallable):
     """laughlin.py:19-100 for N = 2 Q1 + 2: log psi of walkers x [N, 2] (per walker, the
     reference's f convention) or data [B, N, 2] (batched), complex128.  No parameters."""
 
@@ -85,9 +111,6 @@ class LaughlinQuasiparticle:
         diff = self.excitation_lz - self.Q1  # laughlin.py:49-52
         if int(diff) != diff or not (-abs(self.Q1) - 1 <= self.excitation_lz <= abs(self.Q1) + 1):
             raise ValueError(f"impossible Lz = {self.excitation_lz} for the quasiparticle (Q1 = {self.Q1})")
-
-    def init(self, key=None, data=None, device=None) -> dict:
-        return {}
 
     def _logpsi(self, x: torch.Tensor) -> torch.Tensor:
         x = x.to(torch.float64)
@@ -107,13 +130,6 @@ class LaughlinQuasiparticle:
         orb = torch.cat([orbitals * jastrow, excited], dim=-1)
         sign, logdet = torch.linalg.slogdet(orb)  # one determinant: log-sum-exp reduces to this
         return logdet + torch.log(sign)
-
-    def __call__(self, params, data: torch.Tensor) -> torch.Tensor:
-        if data.dim() == 2:
-            return self._logpsi(data)
-        return torch.vmap(self._logpsi)(data)
-
-    apply = __call__
 
 
 __all__ = ["Laughlin", "LaughlinQuasiparticle", "laughlin_q1", "_lib", "_ptr", "_stream"]

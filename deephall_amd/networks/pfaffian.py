@@ -23,7 +23,7 @@ import math
 
 import torch
 
-from .laughlin import Laughlin, analytic_spec
+from .laughlin import Laughlin, TrialCallable
 
 
 def check_pfaffian(nspins, flux, cf_flux: int = 1) -> int:
@@ -42,19 +42,14 @@ def check_pfaffian(nspins, flux, cf_flux: int = 1) -> int:
 class MooreRead(Laughlin):
     """Parameter-free analytic wavefunction on pfaffian.hip."""
 
-    def __init__(self, nspins, flux, cf_flux: int = 1, system=None):
-        self.nspins = tuple(int(n) for n in nspins)
-        self.flux = int(flux)
-        self.cf_flux = int(cf_flux)
-        self.Q = self.flux / 2
-        check_pfaffian(self.nspins, self.flux, self.cf_flux)
-        self.spec = analytic_spec(system, nspins=self.nspins, flux=self.flux, network_type="pfaffian",
-                                  cf_flux=self.cf_flux)
-        self._flat_cache = {}
-        self._epoch = 0
+    name = "Moore-Read"
+    network_type = "pfaffian"
 
-    def vjp(self, *args, **kwargs):
-        raise TypeError("the Moore-Read wavefunction has no parameters to differentiate")
+    def __init__(self, nspins, flux, cf_flux: int = 1, system=None):
+        self._sphere(nspins, flux)
+        self.cf_flux = int(cf_flux)
+        check_pfaffian(self.nspins, self.flux, self.cf_flux)
+        self.spec = self._spec(system, cf_flux=self.cf_flux)
 
 
 def log_pfaffian(A: torch.Tensor) -> torch.Tensor:
@@ -80,9 +75,8 @@ def log_pfaffian(A: torch.Tensor) -> torch.Tensor:
     return out + torch.log(A[0, 1])
 
 
-class MooreReadCallable:
-    """log psi of walkers x [N, 2] (per walker, the reference's f convention) or data
-    [B, N, 2] (batched), complex128.  No parameters."""
+class MooreReadCallable(TrialCallable):
+    """`MooreRead` through `log_pfaffian` (see `TrialCallable`)."""
 
     def __init__(self, nspins, flux, cf_flux: int = 1, system=None):
         self.nspins = tuple(int(n) for n in nspins)
@@ -90,9 +84,6 @@ class MooreReadCallable:
         self.cf_flux = int(cf_flux)
         self.system = system
         check_pfaffian(self.nspins, self.flux, self.cf_flux)
-
-    def init(self, key=None, data=None, device=None) -> dict:
-        return {}
 
     @staticmethod
     def pair_matrix(x: torch.Tensor):
@@ -109,13 +100,6 @@ class MooreReadCallable:
         A, w = self.pair_matrix(x)
         pair = torch.sum(torch.triu(torch.log(w), diagonal=1))  # sum_{i<k} log w_ik
         return log_pfaffian(A) + 2 * self.cf_flux * pair
-
-    def __call__(self, params, data: torch.Tensor) -> torch.Tensor:
-        if data.dim() == 2:
-            return self._logpsi(data)
-        return torch.vmap(self._logpsi)(data)
-
-    apply = __call__
 
 
 __all__ = ["MooreRead", "MooreReadCallable", "log_pfaffian", "check_pfaffian"]

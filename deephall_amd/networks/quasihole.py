@@ -39,7 +39,7 @@ import math
 
 import torch
 
-from .laughlin import Laughlin, analytic_spec
+from .laughlin import Laughlin, TrialCallable
 from .pfaffian import log_pfaffian
 
 MAX_HOLES = 8
@@ -122,25 +122,19 @@ def check_quasihole(nspins, flux, base="halperin", holes=(), species=None, pairi
 class Quasihole(Laughlin):
     """Parameter-free analytic wavefunction on quasihole.hip."""
 
+    name = "quasihole"
+    network_type = "quasihole"
+
     def __init__(self, nspins, flux, base="halperin", holes=(), species=None, pairing=None, exponents=(3, 3, 2),
                  cf_flux: int = 1, system=None):
-        self.nspins = tuple(int(n) for n in nspins)
-        self.flux = int(flux)
+        self._sphere(nspins, flux)
         self.state = check_quasihole(self.nspins, self.flux, base, holes, species, pairing, exponents, cf_flux)
         self.base, self.exponents, self.cf_flux, self.holes = self.state
-        self.Q = self.flux / 2
-        self.spec = analytic_spec(system, nspins=self.nspins, flux=self.flux, network_type="quasihole",
-                                  quasihole=self.state)
-        self._flat_cache = {}
-        self._epoch = 0
-
-    def vjp(self, *args, **kwargs):
-        raise TypeError("the quasihole wavefunction has no parameters to differentiate")
+        self.spec = self._spec(system, quasihole=self.state)
 
 
-class QuasiholeCallable:
-    """log psi of walkers x [N, 2] (per walker, the reference's f convention) or data
-    [B, N, 2] (batched), complex128.  No parameters."""
+class QuasiholeCallable(TrialCallable):
+    """`Quasihole` in torch operations (see `TrialCallable`)."""
 
     def __init__(self, nspins, flux, base="halperin", holes=(), species=None, pairing=None, exponents=(3, 3, 2),
                  cf_flux: int = 1, system=None):
@@ -163,9 +157,6 @@ class QuasiholeCallable:
         self._acts = torch.stack([torch.ones(N, dtype=torch.bool) if k == "both" else up if k == "up" else ~up
                                   if k == "down" else torch.zeros(N, dtype=torch.bool) for k in kinds], dim=1)
         self._groups = tuple([a for a, k in enumerate(kinds) if k == g] for g in ("A", "B"))
-
-    def init(self, key=None, data=None, device=None) -> dict:
-        return {}
 
     def _logpsi(self, x: torch.Tensor) -> torch.Tensor:
         x = x.to(torch.float64)
@@ -190,13 +181,6 @@ class QuasiholeCallable:
             A = (1.0 - eye) * (F[:, None] * G[None, :] + F[None, :] * G[:, None]) / (w + eye)
             out = out + log_pfaffian(A)
         return out
-
-    def __call__(self, params, data: torch.Tensor) -> torch.Tensor:
-        if data.dim() == 2:
-            return self._logpsi(data)
-        return torch.vmap(self._logpsi)(data)
-
-    apply = __call__
 
 
 __all__ = ["Quasihole", "QuasiholeCallable", "check_quasihole"]
