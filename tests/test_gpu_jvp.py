@@ -18,7 +18,7 @@ import torch
 
 from deephall_amd.networks.psiformer import ParamTree
 from helpers import make_params, make_walkers, oracle_config, to_device_params
-from test_gpu_ntk import GATE_X, jacobian32, jacobian64
+from test_gpu_ntk import GATE_X, NAMES, jacobian32, jacobian64
 from test_gpu_parity import build
 
 pytestmark = pytest.mark.gpu
@@ -52,13 +52,16 @@ def case(name, cuda):
     return c
 
 
-@pytest.mark.parametrize("name", ["C1", "C2", "MIX"])
+@pytest.mark.parametrize("name", NAMES)
 def test_matches_float64_oracle(cuda, name):
     """e <= 4 e0 per config.  Measured on the MI355X (the kernel contracts the batch-mean-centred
     rows):
         C1  (N = 3, D = 256, B = 45):  e = 8.887e-08, e0 = 8.836e-08  (e / e0 = 1.01)
         C2  (N = 6, D = 256, B = 24):  e = 2.550e-08, e0 = 2.864e-08  (0.89)
         MIX (N = 4, D = 16,  B = 35):  e = 4.445e-07, e0 = 4.493e-07  (0.99)
+        C4  (N = 10, D = 256, B = 15): e = 3.091e-08, e0 = 2.951e-08  (1.05)
+        C5  (N = 20, D = 256, B = 9):  e = 1.089e-08, e0 = 1.114e-08  (0.98)
+        MIX32 (N = 3 + 2, D = 16, B = 28): e = 6.299e-08, e0 = 6.063e-08  (1.04)
     The worst walker is the f32 rows' worst in every config: the error is the forward and reverse
     passes', not the product's.  A build that contracts the raw rows instead (DH_NTK_JVP_RAW)
     shows no difference at these sizes."""
@@ -78,7 +81,7 @@ def test_matches_float64_oracle(cuda, name):
     assert e <= GATE_X * e0, (e, e0)
 
 
-@pytest.mark.parametrize("name", ["C1", "C2", "MIX"])
+@pytest.mark.parametrize("name", NAMES)
 def test_exactness(cuda, name):
     """Linear in v to the bit for a power of two, reproducible, the same jv with and without T
     and on every part, and T the bits of dh_ntk / dh_ntk_part."""
@@ -95,7 +98,7 @@ def test_exactness(cuda, name):
         assert torch.equal(Tp, model.ntk(params, xd, ctd, part=part, nparts=2, mirror=False)), part
 
 
-@pytest.mark.parametrize("name", ["C1", "C2", "MIX"])
+@pytest.mark.parametrize("name", NAMES)
 def test_zero_cotangents(cuda, name):
     """Zero cotangents on three walkers, one of them in the partial tile: exactly 0 there, every
     other entry bit-identical."""

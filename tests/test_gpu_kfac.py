@@ -27,12 +27,13 @@ import torch
 
 from deephall_amd import Config, train
 from deephall_amd.networks.psiformer import ParamTree
-from helpers import make_params, make_walkers, oracle_config, to_device_params
+from helpers import grad_f32_errors, make_params, make_walkers, oracle_config, to_device_params
 from oracle import kfac as KF
 from oracle import reference as R
 from test_gpu_parity import build
 
 pytestmark = pytest.mark.gpu
+TOL_G = 3e-5  # test_gpu_grad.py: the gradient gate the 1.5e-4 of the statistics is derived from
 
 
 def _slots(model, cuda):
@@ -56,13 +57,29 @@ def _oracle_by_slot(lay, ocfg, stats, diag):
     return out, gen
 
 
-@pytest.mark.parametrize("name,B,layers,orbital", [("C1", 8, 2, "full"), ("MIX", 8, 1, "full"), ("C2", 6, 2, "full"),
-                                                   ("C1", 8, 1, "sparse"), ("MIX", 6, 1, "sparse"),
-                                                   ("C2", 4, 1, "sparse")])
+STAT_CASES = [("C1", 8, 2, "full"), ("MIX", 8, 1, "full"), ("C2", 6, 2, "full"), ("C1", 8, 1, "sparse"),
+              ("MIX", 6, 1, "sparse"), ("C2", 4, 1, "sparse")]
+# N = 10 and 20 (orbital factors of 240^2 and 1160^2 entries), unequal spin blocks
+STAT_CASES_EDGE = [("C4", 4, 2, "full"), ("C5", 2, 2, "full"), ("MIX32", 8, 1, "full"), ("MIX32", 6, 1, "sparse")]
+
+
+@pytest.mark.parametrize("name,B,layers,orbital", STAT_CASES + STAT_CASES_EDGE)
 def test_kfac_statistics_match_oracle(cuda, name, B, layers, orbital):
     """Every factor slot and the generic diagonal; "sparse" orbitals (blocks.py:52-62) add the
     8 N K-output featured blocks, the complex lll_weight block (kfac.py:127-133, 175-181;
-    oracle/kfac.py header) and its generic bias."""
+    oracle/kfac.py header) and its generic bias.
+
+    The 1.5e-4 stands on the gradient tests' 3e-5 per tensor (the header), which the oracle's own
+    float32 run no longer meets at N = 20 (test_grad_floor_host.py).  For a case of
+    STAT_CASES_EDGE the bound is therefore scaled by max(1, worst e32 / 3e-5), e32 =
+    helpers.grad_f32_errors on this case's walkers with the cotangent (1, 0).  The cases of
+    STAT_CASES keep the bare 1.5e-4 (asserted): the scale is not applied to them.  (It would not be
+    1 for all of them: at C2, B = 6 a layer-1 query bias of the float32 run is off by 1.5e-4.)
+    Measured on the MI355X, worst factor error (e32 and the bound of the edge cases):
+        C1 3.5e-06, MIX 1.9e-06, C2 8.7e-05, C1 sparse 5.1e-06, MIX sparse 7.8e-06, C2 sparse 1.0e-05
+        C4 3.4e-05 (1.4e-05, 1.5e-04)          MIX32 2.0e-06 (4.4e-06, 1.5e-04)
+        C5 5.1e-05 (3.0e-05, 1.5e-04)          MIX32 sparse 3.5e-06 (3.9e-06, 1.5e-04)
+    (e32 differs from one CPU to another: 5.2e-05 at C5 on a second machine, bound 2.6e-04.)"""
     ocfg = oracle_config(name, num_layers=layers, orbital=orbital)
     p64 = make_params(ocfg)
     system, model = build(ocfg)
@@ -83,21 +100,31 @@ def test_kfac_statistics_match_oracle(cuda, name, B, layers, orbital):
         errs[slot] = (got - M).abs().max().item() / max(M.abs().max().item(), 1e-30)
     print({k: f"{v:.1e}" for k, v in sorted(errs.items())})
     worst = max(errs.values())
-    assert worst < 1.5e-4, errs
+    tol = 1.5e-4
+    if (name, B, layers, orbital) in STAT_CASES_EDGE:
+        ct = np.zeros((B, 2))
+        ct[:, 0] = 1.0
+        e32 = max(grad_f32_errors(p64, ocfg, x, ct).values())
+        tol *= max(1.0, e32 / TOL_G)
+        print(f"{name} {orbital}: worst f32 gradient tensor {e32:.1e}, factor bound {tol:.2e}")
+    assert tol == 1.5e-4 or (name, B, layers, orbital) in STAT_CASES_EDGE
+    assert worst < tol, errs
     g_got = st[lay["nmat"]: lay["nmat"] + lay["ngeneric"]]
     gerr = (g_got - gen).abs().max().item() / gen.abs().max().item()
     print(f"{name}: worst factor {worst:.1e}, generic {gerr:.1e}")
     assert gerr < 1e-4
 
 
-def test_kfac_vjp_with_cotangent_and_chunks(cuda):
+@pytest.mark.parametrize("name,layers", [("C1", 2), ("MIX32", 1)], ids=["C1", "MIX32"])
+def test_kfac_vjp_with_cotangent_and_chunks(cuda, name, layers):
     """The training path of dh_kfac_vjp: a real cotangent (the gradient's and the
     Fisher pass share one saved forward) and walker chunks (the statistics accumulated across
     chunks, api_grad.cpp's acc).  The statistics equal the ct=None single-chunk result, the
-    returned gradient equals model.vjp's, and the chunked run equals the unchunked one."""
+    returned gradient equals model.vjp's, and the chunked run equals the unchunked one.
+    MIX32 (3 up, 2 down): the per-block gathers of unequal blocks accumulate over chunks."""
     from deephall_amd.networks import psiformer as pf
 
-    ocfg = oracle_config("C1", num_layers=2)
+    ocfg = oracle_config(name, num_layers=layers)
     p64 = make_params(ocfg)
     system, model = build(ocfg)
     params = to_device_params(p64)
