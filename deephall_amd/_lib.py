@@ -115,9 +115,15 @@ EXPORTS = [
     "dh_sf_multipoles",
     "dh_sf_accumulate",
     "dh_create_quasihole",
+    "dh_hole_table_bytes",
+    "dh_hole_table",
+    "dh_hole_workspace_bytes",
+    "dh_hole_logs",
+    "dh_hole_gram",
 ]
 
 DH_QUASIHOLE_MAX_HOLES = 8
+DH_HOLE_MAX_CONFIGS = 16
 QUASIHOLE_BASES = {"halperin": 0, "pfaffian": 1}  # DH_QUASIHOLE_*
 HOLE_KINDS = {"both": 0, "up": 1, "down": 2, "A": 3, "B": 4}  # DH_HOLE_*
 
@@ -172,6 +178,25 @@ class DhQuasihole(C.Structure):
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
         self.struct_size = C.sizeof(DhQuasihole)
+
+
+class DhHoleConfigs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", C.c_int),
+        ("m_up", C.c_int),
+        ("m_dn", C.c_int),
+        ("n_inter", C.c_int),
+        ("p", C.c_int),
+        ("n_holes", C.c_int),
+        ("n_configs", C.c_int),
+        ("kind", (C.c_int * DH_QUASIHOLE_MAX_HOLES) * DH_HOLE_MAX_CONFIGS),
+        ("holes", ((C.c_double * 2) * DH_QUASIHOLE_MAX_HOLES) * DH_HOLE_MAX_CONFIGS),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(DhHoleConfigs)
 
 
 _lib = None
@@ -321,6 +346,16 @@ def load(path: Path | str | None = None):
     lib.dh_create_halperin.restype = i32
     lib.dh_create_quasihole.argtypes = [C.POINTER(DhConfig), C.POINTER(DhQuasihole), C.POINTER(vp)]
     lib.dh_create_quasihole.restype = i32
+    lib.dh_hole_table_bytes.argtypes = []
+    lib.dh_hole_table_bytes.restype = sz
+    lib.dh_hole_table.argtypes = [C.POINTER(DhConfig), C.POINTER(DhHoleConfigs), vp, sz]
+    lib.dh_hole_table.restype = i32
+    lib.dh_hole_workspace_bytes.argtypes = [i32, i32]
+    lib.dh_hole_workspace_bytes.restype = sz
+    lib.dh_hole_logs.argtypes = [C.POINTER(DhConfig), C.POINTER(DhHoleConfigs), vp, i32, vp, sz, vp, vp]
+    lib.dh_hole_logs.restype = i32
+    lib.dh_hole_gram.argtypes = [vp, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.dh_hole_gram.restype = i32
     lib.dh_spin_workspace_bytes.argtypes = [i32, i32, i32]
     lib.dh_spin_workspace_bytes.restype = sz
     lib.dh_spin_exchange.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp]

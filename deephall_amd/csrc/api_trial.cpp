@@ -1,7 +1,11 @@
 // The host side of the parameter-free trial states (laughlin.hip, cf.hip, pfaffian.hip, halperin.hip,
 // quasihole.hip): what each state asks of N, the flux and its own arguments, the handle it gets, and
-// the one launcher behind dh_logpsi, dh_mcmc_step and dh_local_energy.
+// the one launcher behind dh_logpsi, dh_mcmc_step and dh_local_energy.  Also the handle-free dh_hole_*
+// calls: a table of hole configurations checked as dh_create_quasihole checks one, log psi of all of
+// them on the same walkers, and the Gram matrix of their ratios.
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 
 #include "api_internal.h"
 
@@ -226,35 +230,37 @@ int create_halperin(const dh_config* cfg, int m_up, int m_dn, int n_int, dh_hand
 }
 
 // Pinned quasiholes (quasihole.hip) on a Halperin or a Pfaffian base: every hole adds one to the
-// degree of the electrons it acts on, a group of k holes k to the degree of every electron
-int create_quasihole(const dh_config* cfg, const dh_quasihole* q, dh_handle** out) {
+// degree of the electrons it acts on, a group of k holes k to the degree of every electron.
+// Everything dh_create_quasihole asks of cfg and q, and the kernel's state with the holes' spinors:
+// shared with the configurations of dh_hole_table.  name starts the messages.
+int quasihole_state(const dh_config* cfg, const dh_quasihole* q, const std::string& name, QuasiholeState& st) {
   const int N = cfg->n_up + cfg->n_dn;
   const bool pf = q->base == DH_QUASIHOLE_PFAFFIAN;
   if (q->base != DH_QUASIHOLE_HALPERIN && !pf)
-    return fail(DH_EINVAL, "Quasihole: base must be DH_QUASIHOLE_HALPERIN or DH_QUASIHOLE_PFAFFIAN, got " +
+    return fail(DH_EINVAL, name + ": base must be DH_QUASIHOLE_HALPERIN or DH_QUASIHOLE_PFAFFIAN, got " +
                                std::to_string(q->base));
-  if (int rc = check_analytic(cfg, "Quasihole", pf ? 2 : 1)) return rc;
+  if (int rc = check_analytic(cfg, name, pf ? 2 : 1)) return rc;
   if (q->n_holes < 1 || q->n_holes > DH_QUASIHOLE_MAX_HOLES)
-    return fail(DH_EINVAL, "Quasihole: need 1 <= n_holes <= " + std::to_string(DH_QUASIHOLE_MAX_HOLES) + ", got " +
+    return fail(DH_EINVAL, name + ": need 1 <= n_holes <= " + std::to_string(DH_QUASIHOLE_MAX_HOLES) + ", got " +
                                std::to_string(q->n_holes) +
                                (q->n_holes == 0 ? (pf ? " (without holes this is the pfaffian state: dh_create)"
                                                       : " (without holes this is the halperin state: dh_create_halperin)")
                                                 : ""));
   int count[5] = {0, 0, 0, 0, 0};
-  QuasiholeState st{};
+  st = QuasiholeState{};
   st.pfaffian = pf;
   st.n_holes = q->n_holes;
   for (int a = 0; a < q->n_holes; ++a) {
     const double th = q->holes[a][0], ph = q->holes[a][1];
     const int kind = q->kind[a];
     if (!std::isfinite(th) || !std::isfinite(ph))
-      return fail(DH_EINVAL, "Quasihole: hole " + std::to_string(a) + " has a non-finite angle");
+      return fail(DH_EINVAL, name + ": hole " + std::to_string(a) + " has a non-finite angle");
     if (th < 0.0 || th > M_PI)
-      return fail(DH_EINVAL, "Quasihole: hole " + std::to_string(a) + " needs 0 <= theta <= pi, got " + std::to_string(th));
+      return fail(DH_EINVAL, name + ": hole " + std::to_string(a) + " needs 0 <= theta <= pi, got " + std::to_string(th));
     const bool ok = pf ? (kind == DH_HOLE_BOTH || kind == DH_HOLE_GROUP_A || kind == DH_HOLE_GROUP_B)
                        : (kind == DH_HOLE_BOTH || kind == DH_HOLE_UP || kind == DH_HOLE_DOWN);
     if (!ok)
-      return fail(DH_EINVAL, "Quasihole: hole " + std::to_string(a) + " has kind " + std::to_string(kind) +
+      return fail(DH_EINVAL, name + ": hole " + std::to_string(a) + " has kind " + std::to_string(kind) +
                                  (pf ? ", the pfaffian base takes DH_HOLE_BOTH, DH_HOLE_GROUP_A and DH_HOLE_GROUP_B"
                                      : ", the halperin base takes DH_HOLE_BOTH, DH_HOLE_UP and DH_HOLE_DOWN"));
     ++count[kind];
@@ -266,28 +272,85 @@ int create_quasihole(const dh_config* cfg, const dh_quasihole* q, dh_handle** ou
   }
   if (pf) {
     const int p = q->p, k = count[DH_HOLE_GROUP_A];
-    if (N % 2) return fail(DH_EINVAL, "Quasihole: the pfaffian base needs an even number of electrons");
-    if (p < 1) return fail(DH_EINVAL, "Quasihole: the pfaffian base needs p >= 1, got " + std::to_string(p));
+    if (N % 2) return fail(DH_EINVAL, name + ": the pfaffian base needs an even number of electrons");
+    if (p < 1) return fail(DH_EINVAL, name + ": the pfaffian base needs p >= 1, got " + std::to_string(p));
     if (count[DH_HOLE_GROUP_B] != k)
-      return fail(DH_EINVAL, "Quasihole: the groups A and B need the same number of holes, got " + std::to_string(k) +
+      return fail(DH_EINVAL, name + ": the groups A and B need the same number of holes, got " + std::to_string(k) +
                                  " and " + std::to_string(count[DH_HOLE_GROUP_B]));
     const int64_t f = moore_read_flux(N, p, k + count[DH_HOLE_BOTH]);
     if (cfg->flux != f)
-      return fail(DH_EINVAL, "Quasihole: the state lives at flux 2 p (N - 1) - 1 + k + (Abelian holes) = " +
+      return fail(DH_EINVAL, name + ": the state lives at flux 2 p (N - 1) - 1 + k + (Abelian holes) = " +
                                  std::to_string(f) + ", got " + std::to_string(cfg->flux));
     st.m_up = st.m_dn = st.n_int = 2 * p;
   } else {
     const int holes[2] = {count[DH_HOLE_BOTH] + count[DH_HOLE_UP], count[DH_HOLE_BOTH] + count[DH_HOLE_DOWN]};
-    if (int rc = check_halperin(cfg, "Quasihole", q->m_up, q->m_dn, q->n_inter, holes)) return rc;
+    if (int rc = check_halperin(cfg, name, q->m_up, q->m_dn, q->n_inter, holes)) return rc;
     st.m_up = q->m_up;
     st.m_dn = q->m_dn;
     st.n_int = q->n_inter;
   }
-  if (int rc = check_lds(n_needs("Quasihole", N), quasihole_smem_bytes(N, pf, true))) return rc;
+  return check_lds(name + ": N = " + std::to_string(N) + " needs", quasihole_smem_bytes(N, pf, true));
+}
+
+int create_quasihole(const dh_config* cfg, const dh_quasihole* q, dh_handle** out) {
+  QuasiholeState st;
+  if (int rc = quasihole_state(cfg, q, "Quasihole", st)) return rc;
   dh_handle* h = analytic_handle(cfg, dh_handle::QUASIHOLE, {});
   h->trial.quasihole = st;
   *out = h;
   return DH_OK;
+}
+
+// The packed table of dh_hole_table: the spinors, then the kinds
+struct HoleTable {
+  double uv[DH_HOLE_MAX_CONFIGS][DH_QUASIHOLE_MAX_HOLES][4];
+  int kind[DH_HOLE_MAX_CONFIGS][DH_QUASIHOLE_MAX_HOLES];
+};
+
+// What dh_hole_table and dh_hole_logs check: the entry (check_entry), the number of configurations,
+// and every configuration as the dh_quasihole it is (quasihole_state).  Fills the table and base,
+// the state of configuration 0: the weights, the base and n_holes are the same in all.
+int hole_table(const dh_config* cfg, const dh_hole_configs* hc, bool args, HoleTable& tab, QuasiholeState& base) {
+  if (int rc = check_entry(args && cfg && hc, cfg, "Holes: ", "Holes", DH_NETWORK_QUASIHOLE, "dh_hole_table",
+                           "DH_NETWORK_QUASIHOLE", "dh_hole_configs", hc ? hc->struct_size : 0, sizeof(dh_hole_configs)))
+    return rc;
+  if (hc->n_configs < 1 || hc->n_configs > DH_HOLE_MAX_CONFIGS)
+    return fail(DH_EINVAL, "Holes: need 1 <= n_configs <= " + std::to_string(DH_HOLE_MAX_CONFIGS) + ", got " +
+                               std::to_string(hc->n_configs));
+  std::memset(&tab, 0, sizeof(tab));
+  for (auto& row : tab.kind)
+    for (int& k : row) k = -1;
+  for (int c = 0; c < hc->n_configs; ++c) {
+    dh_quasihole q{};
+    q.struct_size = sizeof(dh_quasihole);
+    q.base = hc->base;
+    q.m_up = hc->m_up;
+    q.m_dn = hc->m_dn;
+    q.n_inter = hc->n_inter;
+    q.p = hc->p;
+    q.n_holes = hc->n_holes;
+    const int nh = std::min(std::max(hc->n_holes, 0), DH_QUASIHOLE_MAX_HOLES);  // the check refuses the rest
+    for (int a = 0; a < nh; ++a) {
+      q.kind[a] = hc->kind[c][a];
+      q.holes[a][0] = hc->holes[c][a][0];
+      q.holes[a][1] = hc->holes[c][a][1];
+    }
+    QuasiholeState st;
+    if (int rc = quasihole_state(cfg, &q, "Holes: configuration " + std::to_string(c), st)) return rc;
+    for (int a = 0; a < st.n_holes; ++a) {
+      tab.kind[c][a] = st.kind[a];
+      for (int j = 0; j < 4; ++j) tab.uv[c][a][j] = st.uv[a][j];
+    }
+    if (c == 0) base = st;
+  }
+  return DH_OK;
+}
+
+const char* hole_gram_error(int B, int K) {
+  if (B < 1) return "Holes: B < 1";
+  if (K < 1 || K > DH_HOLE_MAX_CONFIGS) return "Holes: n_configs outside 1..DH_HOLE_MAX_CONFIGS";
+  if ((int64_t)B * K > INT32_MAX) return "Holes: B n_configs >= 2^31";
+  return nullptr;
 }
 
 }  // namespace
@@ -334,6 +397,44 @@ int dh_create_quasihole(const dh_config* cfg, const dh_quasihole* q, dh_handle**
   const int rc = check_entry(cfg && q && out, cfg, "Quasihole: ", "Quasihole", DH_NETWORK_QUASIHOLE, "dh_create_quasihole",
                              "DH_NETWORK_QUASIHOLE", "dh_quasihole", q ? q->struct_size : 0, sizeof(dh_quasihole));
   return rc ? rc : create_quasihole(cfg, q, out);
+}
+
+size_t dh_hole_table_bytes(void) { return sizeof(HoleTable); }
+
+int dh_hole_table(const dh_config* cfg, const dh_hole_configs* configs, void* table_host, size_t bytes) {
+  HoleTable tab;
+  QuasiholeState base;
+  if (int rc = hole_table(cfg, configs, table_host != nullptr, tab, base)) return rc;
+  if (bytes < sizeof(HoleTable)) return fail(DH_EINVAL, "Holes: table smaller than dh_hole_table_bytes");
+  std::memcpy(table_host, &tab, sizeof(tab));
+  return DH_OK;
+}
+
+size_t dh_hole_workspace_bytes(int B, int n_configs) {
+  if (hole_gram_error(B, n_configs)) return 0;
+  return align64(hole_workspace_bytes(B, n_configs));
+}
+
+int dh_hole_logs(const dh_config* cfg, const dh_hole_configs* configs, const float* x, int B, const void* table,
+                 size_t table_bytes, double* L, void* stream) {
+  HoleTable tab;  // checked and discarded: the kernel reads the caller's device copy
+  QuasiholeState base;
+  if (int rc = hole_table(cfg, configs, x && table && L, tab, base)) return rc;
+  if (const char* e = hole_gram_error(B, configs->n_configs)) return fail(DH_EINVAL, e);
+  if ((int64_t)B * (cfg->n_up + cfg->n_dn) > INT32_MAX) return fail(DH_EINVAL, "Holes: B nelec >= 2^31");
+  if (table_bytes < sizeof(HoleTable)) return fail(DH_EINVAL, "Holes: table smaller than dh_hole_table_bytes");
+  launch_hole_logs(x, B, cfg->n_up + cfg->n_dn, cfg->n_up, base, configs->n_configs, table, L, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_hole_gram(const double* L, int B, int n_configs, const double* shift, double* S, int32_t* nvalid,
+                 void* workspace, size_t workspace_bytes, void* stream) {
+  if (!L || !shift || !S || !nvalid || !workspace) return fail(DH_EINVAL, "Holes: null pointer");
+  if (const char* e = hole_gram_error(B, n_configs)) return fail(DH_EINVAL, e);
+  if (workspace_bytes < dh_hole_workspace_bytes(B, n_configs))
+    return fail(DH_ENOMEM, "Holes: workspace smaller than dh_hole_workspace_bytes");
+  launch_hole_gram(L, B, n_configs, shift, S, nvalid, workspace, (hipStream_t)stream);
+  return check_launch();
 }
 
 int dh_create_halperin(const dh_config* cfg, int m_up, int m_dn, int n_inter, dh_handle** out) {

@@ -525,6 +525,16 @@ struct QuasiholeState {
 size_t quasihole_smem_bytes(int N, bool pfaffian, bool energy);
 void launch_quasihole(const Dims& d, const float* x, const QuasiholeState& q, float* logpsi, float* e_l, float* obs,
                       int nw, hipStream_t s);
+// out[B][K][2] (double) = log psi_c of each walker for the K configurations of a device table
+// (dh_hole_table's layout: uv [DH_HOLE_MAX_CONFIGS][DH_QUASIHOLE_MAX_HOLES][4] double, then kind
+// [DH_HOLE_MAX_CONFIGS][DH_QUASIHOLE_MAX_HOLES] int); base: the weights, the base and n_holes.
+void launch_hole_logs(const float* x, int B, int N, int n_up, const QuasiholeState& base, int K, const void* table,
+                      double* out, hipStream_t s);
+
+// holes.hip: the Gram matrix of the amplitude ratios over the walkers (dh_hole_gram)
+size_t hole_workspace_bytes(int B, int K);
+void launch_hole_gram(const double* L, int B, int K, const double* shift, double* S, int32_t* nvalid, void* workspace,
+                      hipStream_t s);
 
 // det.hip: backward of log psi = J + log sum_k det Phi_k for per-walker cotangents ct[nw][2]:
 // dF [nw*N][ld_orb] (all columns written) and jg[nw][2] = ct.re * dJ / d(ee_par, ee_anti)

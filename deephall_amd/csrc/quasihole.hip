@@ -36,6 +36,9 @@
 // block) in both instantiations: they give the same bits.
 // LDS in complex doubles: energy, Halperin base 4 N^2 + 14 N + 20; energy, Pfaffian base
 // 11 N^2 + 29 N + 20 (N <= 28 in 160 KiB); value 2 N + 20 and N^2 + 6 N + 20.
+//
+// hole_logs_kernel (dh_hole_logs) is the value kernel over a table of hole configurations on the
+// same walkers, its result kept in double: the input of the overlap matrix of holes.hip.
 #include "trial_common.h"
 
 namespace dh {
@@ -321,6 +324,69 @@ __global__ __launch_bounds__(64) void quasihole_kernel(const float* __restrict__
   hamiltonian_tail(x, b, N, g, H, Q, radius, lambda, interaction, logpf, lrest, e_l, obs, tid, nt);
 }
 
+// log psi_c of one walker for the K hole configurations of a table (dh_hole_logs), complex double.
+// The value layout of quasihole_kernel<PF, false> and its functions, so that out[b][c] rounded to
+// float32 is dh_logpsi of a handle with configuration c, bit for bit: the electrons' spinors and
+// the pair part are formed once per walker, the holes of configuration c then take the place of
+// the by-value argument in HU and kind, and on the Pfaffian base A is rebuilt in the same LDS and
+// eliminated once per configuration.  uv [K][kMaxHoles][4] and knd [K][kMaxHoles] are the device
+// table; every bound (N, nh, K) is a host-checked argument, none is read from the table.
+template <bool PF>
+__global__ __launch_bounds__(64) void hole_logs_kernel(const float* __restrict__ x, const double* __restrict__ uv,
+                                                       const int* __restrict__ knd, double* __restrict__ out, int N,
+                                                       int n_up, int m_up, int m_dn, int n_int, int nh, int K) {
+  extern __shared__ double smd[];
+  zd* sm = reinterpret_cast<zd*>(smd);
+  const QSm L = qsm_layout(N, PF, false);
+  constexpr int SU = 2;
+  zd *UV = sm + L.uv, *HU = sm + L.hole, *logpf = sm + L.lp;
+  int* kind = reinterpret_cast<int*>(sm + L.kind);
+  double* pivd = &logpf[1].re;
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  for (int i = tid; i < N; i += nt)
+    uv_derivs<false>((double)x[2 * ((size_t)b * N + i)], (double)x[2 * ((size_t)b * N + i) + 1], UV + SU * i);
+  __syncthreads();
+  const zd lpair = pair_log(UV, SU, N, n_up, m_up, m_dn, n_int, tid);
+  for (int c = 0; c < K; ++c) {
+    __syncthreads();  // configuration c - 1 has been read
+    if (tid < kMaxHoles) {
+      const bool on = tid < nh;
+      const double* h = uv + 4 * ((size_t)c * kMaxHoles + tid);
+      HU[2 * tid] = on ? zd{h[0], h[1]} : zd{0.0, 0.0};
+      HU[2 * tid + 1] = on ? zd{h[2], h[3]} : zd{0.0, 0.0};
+      kind[tid] = on ? knd[c * kMaxHoles + tid] : -1;
+    }
+    if (tid == 0) *logpf = zd{0.0, 0.0};
+    __syncthreads();
+    if (PF) {
+      zd *FG = sm + L.fg, *G = sm + L.G, *f0 = sm + L.misc, *f1 = f0 + N;
+      bool grouped = false;
+      for (int a = 0; a < nh; ++a) grouped = grouped || kind[a] == DH_HOLE_GROUP_A;
+      for (int idx = tid; idx < 2 * N; idx += nt) {
+        const int i = idx >> 1, grp = idx & 1;
+        group_product<false>(UV + SU * i, HU, kind, nh, grp ? DH_HOLE_GROUP_B : DH_HOLE_GROUP_A,
+                             grp && !grouped ? 0.5 : 1.0, FG + SU * i + grp);
+      }
+      __syncthreads();
+      for (int idx = tid; idx < N * N; idx += nt) {
+        const int i = idx / N, k = idx % N;
+        const zd *qi = UV + SU * i, *qk = UV + SU * k, *Fi = FG + SU * i, *Fk = FG + SU * k;
+        zd a{0.0, 0.0};
+        if (i != k) a = (Fi[0] * Fk[1] + Fk[0] * Fi[1]) * zinv(qi[0] * qk[1] - qk[0] * qi[1]);
+        G[i * N + k] = a;
+      }
+      __syncthreads();
+      skew_eliminate<false>(G, N, N, f0, f1, nullptr, logpf, pivd, tid, nt);
+    }
+    const zd lrest = lpair + hole_log(UV, SU, N, n_up, HU, kind, nh, tid);
+    if (tid == 0) {
+      double* o = out + 2 * ((size_t)b * K + c);
+      o[0] = logpf->re + lrest.re;
+      o[1] = remainder(logpf->im + lrest.im, 2.0 * M_PI);
+    }
+  }
+}
+
 template <bool PF>
 void launch_quasihole_b(const Dims& d, const float* x, const QuasiholeState& q, float* logpsi, float* e_l, float* obs,
                         int nw, hipStream_t s) {
@@ -348,6 +414,19 @@ void launch_quasihole(const Dims& d, const float* x, const QuasiholeState& q, fl
     launch_quasihole_b<true>(d, x, q, logpsi, e_l, obs, nw, s);
   else
     launch_quasihole_b<false>(d, x, q, logpsi, e_l, obs, nw, s);
+}
+
+void launch_hole_logs(const float* x, int B, int N, int n_up, const QuasiholeState& base, int K, const void* table,
+                      double* out, hipStream_t s) {
+  const double* uv = static_cast<const double*>(table);
+  const int* knd = reinterpret_cast<const int*>(uv + (size_t)DH_HOLE_MAX_CONFIGS * kMaxHoles * 4);
+  const size_t bytes = quasihole_smem_bytes(N, base.pfaffian, false);  // at most 20 KiB (N = 32)
+  if (base.pfaffian)
+    hipLaunchKernelGGL(hole_logs_kernel<true>, dim3(B), dim3(64), bytes, s, x, uv, knd, out, N, n_up, base.m_up,
+                       base.m_dn, base.n_int, base.n_holes, K);
+  else
+    hipLaunchKernelGGL(hole_logs_kernel<false>, dim3(B), dim3(64), bytes, s, x, uv, knd, out, N, n_up, base.m_up,
+                       base.m_dn, base.n_int, base.n_holes, K);
 }
 
 }  // namespace dh

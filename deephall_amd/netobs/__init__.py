@@ -23,6 +23,10 @@ with the same names, options, value/state keys and digests:
   (observables/structure_factor.py, not in the reference) needs the walkers only: the Legendre pair
   sums, the multipoles sum_i Y_LM and their reduction over walkers in double are csrc/sfactor.hip
   (``dh_sf_*``);
+* the overlap matrix of a pinned-quasihole state with its holes moved (observables/hole_overlap.py,
+  not in the reference): log psi of K hole configurations on the same walkers in double and the
+  K x K Gram matrix of their ratios are csrc/quasihole.hip and csrc/holes.hip (``dh_hole_*``);
+  holonomy.py turns the overlaps into Berry phases and non-Abelian holonomies on the host;
 * every wavefunction value goes through ``dh_logpsi`` (Psiformer or the native Laughlin
   state), the walk through ``dh_mcmc_step``;
 * ``evaluate`` is a minimal stand-in for NetObs's own evaluation loop (restore, burn-in,
@@ -34,7 +38,8 @@ with the same names, options, value/state keys and digests:
 from .adaptor import DeepHallAdaptor, DeepHallAuxData
 from .estimator import Estimator, Observable, evaluate
 from .hall_system import HallSystem
-from .observables import density, ll_rdm, one_rdm, overlap, pair_corr, renyi2, spin_square, structure_factor
+from .observables import (density, hole_overlap, ll_rdm, one_rdm, overlap, pair_corr, renyi2, spin_square,
+                          structure_factor)
 
 
 class _Registry(dict):
@@ -64,6 +69,7 @@ EXTRA_ESTIMATORS = _Registry({
     "ll_rdm": ll_rdm.DEFAULT,
     "spin_square": spin_square.DEFAULT,
     "structure_factor": structure_factor.DEFAULT,
+    "hole_overlap": hole_overlap.DEFAULT,
 })
 
 # The own keys are the reference's ``deephall@`` names, so the registry still lists exactly what

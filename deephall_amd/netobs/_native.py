@@ -327,3 +327,111 @@ def sf_accumulate_host(x: torch.Tensor, n_up: int, lmax: int, multipoles: bool =
     """sf_accumulate's results as host tensors, brought over in one device read."""
     out, nl, nlm = _sf_accumulate_packed(x, n_up, lmax, multipoles)
     return _sf_unpack(out.cpu(), nl, nlm, multipoles)
+
+
+# ---- quasihole overlap matrix (csrc/quasihole.hip hole_logs_kernel, csrc/holes.hip) ---------------
+
+class HoleTable:
+    """K configurations of the pinned holes of one quasihole system, checked by ``dh_hole_table``:
+    ``cfg`` and ``configs`` (the C structs), ``host`` (the packed table, uint8) and its device copies."""
+
+    def __init__(self, cfg: _lib.DhConfig, configs: _lib.DhHoleConfigs, host: torch.Tensor):
+        self.cfg, self.configs, self.host = cfg, configs, host
+        self.n_configs, self.n_holes = int(configs.n_configs), int(configs.n_holes)
+        self.nelec = int(cfg.n_up) + int(cfg.n_dn)
+        self._device = {}
+
+    @property
+    def spinors(self) -> torch.Tensor:
+        """[n_configs, n_holes, 2] complex128: (U, V) of hole a of configuration c, as the kernels hold them."""
+        n = _lib.DH_HOLE_MAX_CONFIGS * _lib.DH_QUASIHOLE_MAX_HOLES * 4
+        uv = self.host[:8 * n].view(torch.float64).reshape(_lib.DH_HOLE_MAX_CONFIGS, _lib.DH_QUASIHOLE_MAX_HOLES, 2, 2)
+        return torch.view_as_complex(uv[:self.n_configs, :self.n_holes].contiguous())
+
+    @property
+    def kinds(self) -> torch.Tensor:
+        """[n_configs, n_holes] int32: DH_HOLE_* of hole a of configuration c."""
+        n = _lib.DH_HOLE_MAX_CONFIGS * _lib.DH_QUASIHOLE_MAX_HOLES
+        kind = self.host[32 * n:36 * n].view(torch.int32).reshape(_lib.DH_HOLE_MAX_CONFIGS, _lib.DH_QUASIHOLE_MAX_HOLES)
+        return kind[:self.n_configs, :self.n_holes]
+
+    def on(self, device) -> torch.Tensor:
+        device = torch.device(device)
+        if device not in self._device:
+            self._device[device] = self.host.to(device)
+        return self._device[device]
+
+
+def hole_configs(configs) -> _lib.DhHoleConfigs:
+    """dh_hole_configs from quasihole states ``(base, (m_up, m_dn, n), p, ((theta, phi, kind), ...))``
+    (``networks.quasihole.check_quasihole``): base, exponents and p of the first, the holes of each."""
+    configs = list(configs)
+    hc = _lib.DhHoleConfigs()
+    hc.n_configs = len(configs)
+    if not configs:
+        return hc
+    if len(configs) > _lib.DH_HOLE_MAX_CONFIGS:
+        raise ValueError(f"Holes: need 1 <= n_configs <= {_lib.DH_HOLE_MAX_CONFIGS}, got {len(configs)}")
+    base, (m_up, m_dn, n), p, holes0 = configs[0]
+    hc.base = _lib.QUASIHOLE_BASES[base]
+    hc.m_up, hc.m_dn, hc.n_inter, hc.p = int(m_up), int(m_dn), int(n), int(p)
+    hc.n_holes = len(holes0)
+    for c, state in enumerate(configs):
+        if (state[0], tuple(state[1]), state[2]) != (base, (m_up, m_dn, n), p) or len(state[3]) != len(holes0):
+            raise ValueError(f"Holes: configuration {c} differs from configuration 0 in its base, exponents, p or "
+                             "number of holes")
+        if len(state[3]) > _lib.DH_QUASIHOLE_MAX_HOLES:
+            raise ValueError(f"Holes: need 1 <= n_holes <= {_lib.DH_QUASIHOLE_MAX_HOLES}, got {len(state[3])}")
+        for a, (theta, phi, kind) in enumerate(state[3]):
+            hc.holes[c][a][0], hc.holes[c][a][1] = float(theta), float(phi)
+            hc.kind[c][a] = _lib.HOLE_KINDS[kind]
+    return hc
+
+
+def hole_table(spec_or_cfg, configs) -> HoleTable:
+    """The checked table of ``configs`` (quasihole states, or a ready ``DhHoleConfigs``) for the system of a
+    ``NetworkSpec`` or a ``DhConfig``.  Host only: no device call."""
+    cfg = spec_or_cfg if isinstance(spec_or_cfg, _lib.DhConfig) else spec_or_cfg.to_c()
+    hc = configs if isinstance(configs, _lib.DhHoleConfigs) else hole_configs(configs)
+    lib = _lib.load()
+    host = torch.zeros(int(lib.dh_hole_table_bytes()), dtype=torch.uint8)
+    _lib.check(lib.dh_hole_table(C.byref(cfg), C.byref(hc), host.data_ptr(), host.numel()))
+    return HoleTable(cfg, hc, host)
+
+
+def hole_logs(x: torch.Tensor, table: HoleTable) -> torch.Tensor:
+    """L[B, K] complex128 on the device: log psi_c of walkers x[B, N, 2] for the K configurations of ``table``;
+    L[:, c] rounded to complex64 is ``dh_logpsi`` of the quasihole state with configuration c."""
+    x = _check_cuda(x)
+    B, N, _ = x.shape
+    if N != table.nelec:
+        raise ValueError(f"hole_logs: walkers of {N} electrons, a table for {table.nelec}")
+    dev = table.on(x.device)
+    L = torch.empty(B, table.n_configs, 2, dtype=torch.float64, device=x.device)
+    _lib.check(_lib.load().dh_hole_logs(C.byref(table.cfg), C.byref(table.configs), _ptr(x), B, _ptr(dev), dev.numel(),
+                                        _ptr(L), _stream(x.device)))
+    return torch.view_as_complex(L)
+
+
+def hole_gram(L: torch.Tensor, shift: torch.Tensor | None = None):
+    """(S[K, K] complex128 on the device, nvalid): S[c, c'] = sum_b conj(r[b, c]) r[b, c'] over the walkers
+    whose logs L[B, K] are all finite, r[b, c] = exp(L[b, c] - L[b, 0] - shift[c]); shift [K] real, None: zeros.
+    nvalid is read back from the device (one synchronisation)."""
+    if not L.is_cuda:
+        raise RuntimeError("NetObs estimators run on the GPU (HIP kernels); got a CPU tensor")
+    Lr = torch.view_as_real(L.to(torch.complex128)).contiguous()
+    B, K, _ = Lr.shape
+    shift = (torch.zeros(K, dtype=torch.float64, device=L.device) if shift is None
+             else torch.as_tensor(shift, dtype=torch.float64).to(L.device).contiguous())
+    if shift.shape != (K,):
+        raise ValueError(f"hole_gram: shift must be [{K}], got {tuple(shift.shape)}")
+    lib = _lib.load()
+    nbytes = int(lib.dh_hole_workspace_bytes(B, K))
+    if nbytes < 1:
+        raise ValueError(f"hole_gram: B = {B}, K = {K} outside B >= 1, 1 <= K <= {_lib.DH_HOLE_MAX_CONFIGS}, B K < 2^31")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=L.device)
+    S = torch.empty(K, K, 2, dtype=torch.float64, device=L.device)
+    nvalid = torch.empty(1, dtype=torch.int32, device=L.device)
+    _lib.check(lib.dh_hole_gram(_ptr(Lr), B, K, _ptr(shift), _ptr(S), _ptr(nvalid), _ptr(ws), ws.numel() * 8,
+                                _stream(L.device)))
+    return torch.view_as_complex(S), int(nvalid.item())

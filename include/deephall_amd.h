@@ -590,6 +590,53 @@ int dh_sf_multipoles(const float* x, int B, int nelec, int n_up, int lmax, doubl
 int dh_sf_accumulate(const float* x, int B, int nelec, int n_up, int lmax, int want_multipoles, double* pair_sums,
                      double* rho_sums, int32_t* nvalid, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Quasihole overlap matrix: K configurations of the pinned holes on the same walkers -------
+ * A configuration is one setting of the holes of a dh_quasihole state: n_holes points and kinds.
+ * All K configurations share the base, the exponents, p and n_holes, and each passes the checks of
+ * dh_create_quasihole against the same dh_config, so all live at the same flux; the kinds may
+ * differ between configurations (the pairings of the Pfaffian base).
+ *
+ * dh_hole_table  checks cfg and configs and fills the packed table on the host (no device call):
+ *                uv[DH_HOLE_MAX_CONFIGS][DH_QUASIHOLE_MAX_HOLES][4] double (Re U, Im U, Re V, Im V,
+ *                the spinors a dh_create_quasihole handle holds; zero where unused), then
+ *                kind[DH_HOLE_MAX_CONFIGS][DH_QUASIHOLE_MAX_HOLES] int (-1 where unused):
+ *                dh_hole_table_bytes() bytes.  The caller copies it to device memory it owns.
+ * dh_hole_logs   L[B][n_configs][2] (re, im; double) = log psi_c(R_b) for walkers x[B][nelec][2]
+ *                float32 and the device copy of the table made from the same cfg and configs (both
+ *                are checked again, on the host); Im reduced as dh_logpsi reduces it.  L[b][c]
+ *                rounded to float32 is dh_logpsi of a dh_create_quasihole handle with configuration
+ *                c, bit for bit.  One workgroup per walker walks the configurations: the electrons'
+ *                spinors and the pair part are formed once per walker.
+ * dh_hole_gram   with r[b][c] = exp(L[b][c] - L[b][0] - shift[c]), shift[n_configs] real (device,
+ *                zeros allowed): S[n_configs][n_configs][2] (re, im; double), S[c][c'] = sum over
+ *                the valid walkers of conj(r[b][c]) r[b][c'], and nvalid (one device int32), their
+ *                number.  A walker with a non-finite entry of L, or a ratio that overflows, is
+ *                dropped.  Double arithmetic, a fixed order, no float atomics: two calls give
+ *                identical bits.
+ * workspace (dh_hole_gram): dh_hole_workspace_bytes(B, n_configs) device bytes, 16-byte aligned.
+ * Checked before any device call, DH_EINVAL with a message that starts "Holes:" otherwise (the
+ * workspace query then returns 0): non-null pointers, the struct sizes, 1 <= n_configs <=
+ * DH_HOLE_MAX_CONFIGS, every configuration, B >= 1, B n_configs < 2^31, the table and workspace
+ * sizes (a short workspace is DH_ENOMEM). */
+#define DH_HOLE_MAX_CONFIGS 16
+typedef struct dh_hole_configs {
+  uint32_t struct_size;                     /* = sizeof(dh_hole_configs) = 2592 bytes             */
+  int base;                                 /* DH_QUASIHOLE_HALPERIN or DH_QUASIHOLE_PFAFFIAN      */
+  int m_up, m_dn, n_inter;                  /* Halperin base: the exponents                        */
+  int p;                                    /* Pfaffian base: 2 p vortices per electron            */
+  int n_holes;                              /* holes of every configuration                        */
+  int n_configs;
+  int kind[DH_HOLE_MAX_CONFIGS][DH_QUASIHOLE_MAX_HOLES];       /* DH_HOLE_* of hole a of config c */
+  double holes[DH_HOLE_MAX_CONFIGS][DH_QUASIHOLE_MAX_HOLES][2]; /* its (theta, phi)               */
+} dh_hole_configs;
+size_t dh_hole_table_bytes(void);
+int dh_hole_table(const dh_config* cfg, const dh_hole_configs* configs, void* table_host, size_t bytes);
+size_t dh_hole_workspace_bytes(int B, int n_configs);
+int dh_hole_logs(const dh_config* cfg, const dh_hole_configs* configs, const float* x, int B, const void* table,
+                 size_t table_bytes, double* L, void* stream);
+int dh_hole_gram(const double* L, int B, int n_configs, const double* shift, double* S, int32_t* nvalid,
+                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- log psi supplied by the caller: the arbitrary-callable boundary ---------------------
  * The reference's make_mcmc_step(batch_network, ...) (mcmc.py:105-150) and
  * make_local_kinetic_energy(f, Q, r) (hamiltonian.py:83-172) accept ANY log psi.  For one
