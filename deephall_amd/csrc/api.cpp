@@ -983,187 +983,6 @@ int dh_potential(dh_handle* h, const float* x, int B, float* pe, void* stream) {
   return check_launch();
 }
 
-int dh_histograms(const float* x, int B, int nelec, int density_bins, int pair_bins, float* density, float* pair,
-                  void* stream) {
-  if (!x || B < 1 || nelec < 1 || density_bins < 0 || pair_bins < 0 || density_bins + pair_bins < 1 ||
-      density_bins + pair_bins > 8192 || (density_bins && !density) || (pair_bins && !pair))
-    return fail(DH_EINVAL, "bad arguments");
-  launch_histograms(x, B, nelec, density_bins, pair_bins, density, pair, (hipStream_t)stream);
-  return check_launch();
-}
-
-int dh_monopole_orbitals(const float* points, int n, int flux, float* out, void* stream) {
-  if (!points || !out || n < 1 || flux < 0 || flux > 126) return fail(DH_EINVAL, "bad arguments");
-  launch_monopole_orbitals(points, n, flux, out, (hipStream_t)stream);
-  return check_launch();
-}
-
-// ---- Renyi-2 swap estimator (swap.hip): no handle, like the histograms ----
-
-namespace {
-// the checks the four swap calls share; thetas == nullptr: the call takes no angles
-const char* swap_args_error(int B, int nelec, int n_up, int n_dn, const float* thetas, int A) {
-  if (B < 2) return "swap: B < 2 (no pair)";
-  if (nelec < 1 || n_up < 0 || n_dn < 0 || n_up + n_dn != nelec) return "swap: n_up + n_dn != nelec or nelec < 1";
-  if (A < 1 || A > kSwapMaxAngles) return "swap: A outside 1..DH_SWAP_MAX_ANGLES";
-  if ((int64_t)2 * A * (B / 2) > INT32_MAX) return "swap: 2 A (B / 2) >= 2^31";
-  if (((int64_t)n_up + 1) * ((int64_t)n_dn + 1) > INT32_MAX / A) return "swap: A (n_up + 1)(n_dn + 1) >= 2^31";
-  for (int a = 0; thetas && a < A; ++a)
-    if (thetas[a] != thetas[a]) return "swap: a theta is NaN";
-  return nullptr;
-}
-SwapThetas swap_thetas(const float* thetas, int A) {
-  SwapThetas th{};
-  for (int a = 0; a < A; ++a) th.t[a] = thetas[a];
-  return th;
-}
-}  // namespace
-
-size_t dh_swap_workspace_bytes(int B, int A) {
-  if (swap_args_error(B, 1, 1, 0, nullptr, A)) return 0;
-  return align64((size_t)A * (B / 2) * sizeof(int32_t));
-}
-
-int dh_swap_classify(const float* x, int B, int nelec, int n_up, int n_dn, const float* thetas, int A,
-                     int32_t* sector, int32_t* counts, void* stream) {
-  if (!x || !thetas || !sector || !counts) return fail(DH_EINVAL, "swap: null pointer");
-  if (const char* e = swap_args_error(B, nelec, n_up, n_dn, thetas, A)) return fail(DH_EINVAL, e);
-  launch_swap_classify(x, B, nelec, n_up, swap_thetas(thetas, A), A, sector, counts, (hipStream_t)stream);
-  return check_launch();
-}
-
-int dh_swap_compact(const float* x, int B, int nelec, int n_up, int n_dn, const float* thetas, int A,
-                    const int32_t* sector, int32_t* start, int32_t* pair, float* xs, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-  if (!x || !thetas || !sector || !start || !pair || !xs || !workspace) return fail(DH_EINVAL, "swap: null pointer");
-  if (const char* e = swap_args_error(B, nelec, n_up, n_dn, thetas, A)) return fail(DH_EINVAL, e);
-  if (workspace_bytes < dh_swap_workspace_bytes(B, A)) return fail(DH_ENOMEM, "workspace too small");
-  launch_swap_compact(x, B, nelec, n_up, swap_thetas(thetas, A), A, sector, (int32_t*)workspace, start, pair, xs,
-                      (hipStream_t)stream);
-  return check_launch();
-}
-
-int dh_swap_reduce(const float* logpsi, const float* logpsi_s, int B, int nelec, int n_up, int n_dn, int A, int M,
-                   const int32_t* pair, const int32_t* sector, const int32_t* start, double* sums, void* stream) {
-  if (!logpsi || !sector || !start || !sums || (M != 0 && (!logpsi_s || !pair)))
-    return fail(DH_EINVAL, "swap: null pointer");
-  if (const char* e = swap_args_error(B, nelec, n_up, n_dn, nullptr, A)) return fail(DH_EINVAL, e);
-  if (M < 0 || (int64_t)M > (int64_t)A * (B / 2)) return fail(DH_EINVAL, "swap: M outside 0..A (B / 2)");
-  launch_swap_reduce(logpsi, logpsi_s, B, (n_up + 1) * (n_dn + 1), A, M, pair, sector, start, sums,
-                     (hipStream_t)stream);
-  return check_launch();
-}
-
-// ---- Landau-level-resolved one-body density matrix (rdm.hip): no handle either ----
-
-namespace {
-const char* rdm_basis_error(int flux, int levels) {
-  if (levels < 1 || levels > kRdmMaxLevels) return "rdm: levels outside 1..DH_RDM_MAX_LEVELS";
-  if (flux < 0 || flux > 126) return "rdm: flux outside 0..126";
-  return nullptr;
-}
-const char* rdm_size_error(int B, int nelec, int P) {
-  if (B < 1 || P < 1) return "rdm: B < 1 or P < 1";
-  if (nelec < 1 || nelec > 32) return "rdm: nelec outside 1..32";
-  if ((int64_t)P * B > (int64_t)1 << 30) return "rdm: P B > 2^30";
-  if ((int64_t)P * B * nelec * nelec > INT32_MAX) return "rdm: P B nelec^2 >= 2^31";
-  return nullptr;
-}
-}  // namespace
-
-int dh_rdm_norb(int flux, int levels) { return rdm_basis_error(flux, levels) ? 0 : rdm_norb(flux, levels); }
-
-size_t dh_rdm_workspace_bytes(int B, int nelec, int flux, int levels, int P) {
-  if (rdm_basis_error(flux, levels) || rdm_size_error(B, nelec, P)) return 0;
-  return align64(rdm_workspace_bytes((int64_t)P * B, flux, levels));
-}
-
-int dh_monopole_harmonics(const float* points, int n, int flux, int levels, float* out, void* stream) {
-  if (!points || !out) return fail(DH_EINVAL, "rdm: null pointer");
-  if (const char* e = rdm_basis_error(flux, levels)) return fail(DH_EINVAL, e);
-  if (n < 1 || (int64_t)n * (flux + 2 * levels - 1) > INT32_MAX) return fail(DH_EINVAL, "rdm: n < 1 or too large");
-  const double* table = nullptr;
-  HIP_TRY(rdm_table(flux, levels, &table));
-  launch_monopole_harmonics(points, n, flux, levels, table, out, (hipStream_t)stream);
-  return check_launch();
-}
-
-int dh_rdm_displace(const float* x, const float* r_prime, int B, int nelec, int P, float* xp, void* stream) {
-  if (!x || !r_prime || !xp) return fail(DH_EINVAL, "rdm: null pointer");
-  if (const char* e = rdm_size_error(B, nelec, P)) return fail(DH_EINVAL, e);
-  launch_rdm_displace(x, r_prime, B, nelec, P, xp, (hipStream_t)stream);
-  return check_launch();
-}
-
-int dh_rdm_accumulate(const float* x, const float* r_prime, const float* logpsi, const float* logpsi_p, int B,
-                      int nelec, int n_up, int flux, int levels, int P, int by_spin, double* rho, int32_t* nvalid,
-                      void* workspace, size_t workspace_bytes, void* stream) {
-  if (!x || !r_prime || !logpsi || !logpsi_p || !rho || !nvalid || !workspace)
-    return fail(DH_EINVAL, "rdm: null pointer");
-  if (const char* e = rdm_basis_error(flux, levels)) return fail(DH_EINVAL, e);
-  if (const char* e = rdm_size_error(B, nelec, P)) return fail(DH_EINVAL, e);
-  if (n_up < 0 || n_up > nelec) return fail(DH_EINVAL, "rdm: n_up outside 0..nelec");
-  if (workspace_bytes < dh_rdm_workspace_bytes(B, nelec, flux, levels, P))
-    return fail(DH_EINVAL, "rdm: workspace smaller than dh_rdm_workspace_bytes");
-  const double* table = nullptr;
-  HIP_TRY(rdm_table(flux, levels, &table));
-  HIP_TRY(launch_rdm_accumulate(x, r_prime, logpsi, logpsi_p, B, nelec, n_up, flux, levels, P, by_spin != 0, table,
-                                rho, nvalid, workspace, (hipStream_t)stream));
-  return check_launch();
-}
-
-// ---- total-spin estimator (spin.hip): no handle either ----
-
-namespace {
-const char* spin_size_error(int B, int n_up, int n_dn) {
-  if (B < 1) return "spin: B < 1";
-  if (n_up < 0 || n_dn < 0 || n_up + n_dn < 1 || n_up + n_dn > 32) return "spin: n_up, n_dn < 0 or n_up + n_dn outside 1..32";
-  if ((int64_t)B * n_up * n_dn > INT32_MAX) return "spin: B n_up n_dn >= 2^31";
-  return nullptr;
-}
-const char* spin_window_error(int n_up, int n_dn, int pair0, int pair1) {
-  if (pair0 < 0 || pair1 <= pair0 || pair1 > n_up * n_dn) return "spin: need 0 <= pair0 < pair1 <= n_up n_dn";
-  return nullptr;
-}
-}  // namespace
-
-size_t dh_spin_workspace_bytes(int B, int n_up, int n_dn) {
-  if (spin_size_error(B, n_up, n_dn)) return 0;
-  return align64(spin_workspace_bytes(B, n_up * n_dn));
-}
-
-int dh_spin_exchange(const float* x, int B, int nelec, int n_up, int n_dn, int pair0, int pair1, float* xs,
-                     void* stream) {
-  if (!x || !xs) return fail(DH_EINVAL, "spin: null pointer");
-  if (const char* e = spin_size_error(B, n_up, n_dn)) return fail(DH_EINVAL, e);
-  if (n_up + n_dn != nelec) return fail(DH_EINVAL, "spin: n_up + n_dn != nelec");
-  if (const char* e = spin_window_error(n_up, n_dn, pair0, pair1)) return fail(DH_EINVAL, e);
-  launch_spin_exchange(x, B, nelec, n_up, n_dn, pair0, pair1, xs, (hipStream_t)stream);
-  return check_launch();
-}
-
-int dh_spin_ratios(const float* logpsi, const float* logpsi_s, int B, int n_up, int n_dn, int pair0, int pair1,
-                   void* workspace, size_t workspace_bytes, void* stream) {
-  if (!logpsi || !logpsi_s || !workspace) return fail(DH_EINVAL, "spin: null pointer");
-  if (const char* e = spin_size_error(B, n_up, n_dn)) return fail(DH_EINVAL, e);
-  if (const char* e = spin_window_error(n_up, n_dn, pair0, pair1)) return fail(DH_EINVAL, e);
-  if (workspace_bytes < dh_spin_workspace_bytes(B, n_up, n_dn))
-    return fail(DH_ENOMEM, "spin: workspace smaller than dh_spin_workspace_bytes");
-  launch_spin_ratios(logpsi, logpsi_s, B, pair0, pair1, workspace, (hipStream_t)stream);
-  return check_launch();
-}
-
-int dh_spin_reduce(const float* logpsi, int B, int n_up, int n_dn, void* workspace, size_t workspace_bytes,
-                   double* s2, double* pairs, double* total, int32_t* nvalid, void* stream) {
-  if (!logpsi || !workspace || !s2 || !total || !nvalid) return fail(DH_EINVAL, "spin: null pointer");
-  if (const char* e = spin_size_error(B, n_up, n_dn)) return fail(DH_EINVAL, e);
-  if (n_up * n_dn > 0 && !pairs) return fail(DH_EINVAL, "spin: null pointer");
-  if (workspace_bytes < dh_spin_workspace_bytes(B, n_up, n_dn))
-    return fail(DH_ENOMEM, "spin: workspace smaller than dh_spin_workspace_bytes");
-  launch_spin_reduce(logpsi, B, n_up, n_dn, workspace, s2, pairs, total, nvalid, (hipStream_t)stream);
-  return check_launch();
-}
-
 // ---- log psi supplied by the caller (arbitrary callables, mcmc.py:105 / hamiltonian.py:83) ----
 
 int dh_mh_init(const float* logpsi, float* lp, int32_t* n_accept, int B, void* stream) {

@@ -1,6 +1,6 @@
 // What the host files of the C ABI share: api.cpp (create / destroy, parameters, the forward
-// Trunk, the value / MCMC / energy passes, debug hooks), api_grad.cpp (the gradient side) and
-// api_trial.cpp (the parameter-free trial states).
+// Trunk, the value / MCMC / energy passes, debug hooks), api_grad.cpp (the gradient side),
+// api_trial.cpp (the parameter-free trial states) and api_netobs.cpp (the handle-free estimators).
 #pragma once
 #include <string>
 #include <vector>
@@ -162,6 +162,8 @@ constexpr int PK_CH = PK_COUNT, PK_L1CH = PK_COUNT + 4, PK_TOTAL = PK_COUNT + 5;
 // uploads the state's table at first use if it has one.
 int create_trial(const dh_config* cfg, dh_handle** out);
 int launch_trial(dh_handle* h, const float* x, float* logpsi, float* e_l, float* obs, int nw, hipStream_t s);
+// api_netobs.cpp: the size check of dh_hole_gram, which dh_hole_logs (api_trial.cpp) shares
+const char* hole_gram_error(int B, int K);
 
 inline int check_common(dh_handle* h, const void* x, int B, void* ws, size_t ws_bytes, size_t need) {
   if (!h) return fail(DH_EINVAL, "null handle");

@@ -346,13 +346,6 @@ int hole_table(const dh_config* cfg, const dh_hole_configs* hc, bool args, HoleT
   return DH_OK;
 }
 
-const char* hole_gram_error(int B, int K) {
-  if (B < 1) return "Holes: B < 1";
-  if (K < 1 || K > DH_HOLE_MAX_CONFIGS) return "Holes: n_configs outside 1..DH_HOLE_MAX_CONFIGS";
-  if ((int64_t)B * K > INT32_MAX) return "Holes: B n_configs >= 2^31";
-  return nullptr;
-}
-
 }  // namespace
 
 int dh::create_trial(const dh_config* cfg, dh_handle** out) {
@@ -410,11 +403,6 @@ int dh_hole_table(const dh_config* cfg, const dh_hole_configs* configs, void* ta
   return DH_OK;
 }
 
-size_t dh_hole_workspace_bytes(int B, int n_configs) {
-  if (hole_gram_error(B, n_configs)) return 0;
-  return align64(hole_workspace_bytes(B, n_configs));
-}
-
 int dh_hole_logs(const dh_config* cfg, const dh_hole_configs* configs, const float* x, int B, const void* table,
                  size_t table_bytes, double* L, void* stream) {
   HoleTable tab;  // checked and discarded: the kernel reads the caller's device copy
@@ -424,16 +412,6 @@ int dh_hole_logs(const dh_config* cfg, const dh_hole_configs* configs, const flo
   if ((int64_t)B * (cfg->n_up + cfg->n_dn) > INT32_MAX) return fail(DH_EINVAL, "Holes: B nelec >= 2^31");
   if (table_bytes < sizeof(HoleTable)) return fail(DH_EINVAL, "Holes: table smaller than dh_hole_table_bytes");
   launch_hole_logs(x, B, cfg->n_up + cfg->n_dn, cfg->n_up, base, configs->n_configs, table, L, (hipStream_t)stream);
-  return check_launch();
-}
-
-int dh_hole_gram(const double* L, int B, int n_configs, const double* shift, double* S, int32_t* nvalid,
-                 void* workspace, size_t workspace_bytes, void* stream) {
-  if (!L || !shift || !S || !nvalid || !workspace) return fail(DH_EINVAL, "Holes: null pointer");
-  if (const char* e = hole_gram_error(B, n_configs)) return fail(DH_EINVAL, e);
-  if (workspace_bytes < dh_hole_workspace_bytes(B, n_configs))
-    return fail(DH_ENOMEM, "Holes: workspace smaller than dh_hole_workspace_bytes");
-  launch_hole_gram(L, B, n_configs, shift, S, nvalid, workspace, (hipStream_t)stream);
   return check_launch();
 }
 

@@ -10,21 +10,19 @@
 //   fidelity_residual_kernel (dh_fidelity_residual): eps_b = 1 - n z_b / S from the combined
 //     sums, the weight of conj(d log psi) in the gradient of -log F.
 //
-// Arithmetic: the inputs are float32, everything from the subtraction on is double.  The phase
-// Im d is folded into [-pi, pi] (remainder) before sincos.  |z_b|^2 is taken from the rounded
-// parts of the z_b that enters S, and the residual's quotient from products rounded one by one
-// (no fused multiply-add), so a single walker gives F = 1 and eps = 0 exactly.  One 1024-thread
-// workgroup reduces a batch in a fixed order — each thread its strided walkers in order, a wave
-// by xor shuffles, the 16 waves in order — so two calls give identical bits; no atomics.
+// Arithmetic: the estimators' convention (estimator_common.h), z_b by amp_ratio.  |z_b|^2 is taken
+// from the rounded parts of the z_b that enters S, and the residual's quotient from products
+// rounded one by one (no fused multiply-add), so a single walker gives F = 1 and eps = 0 exactly.
+// One 1024-thread workgroup reduces a batch: each thread its strided walkers in order, a wave by
+// wave_sum, then thread q adds component q of the 16 waves in order.
 #include "dh_internal.h"
-#include "device_common.h"
+#include "estimator_common.h"
 
 namespace dh {
 namespace {
 
 constexpr int kNT = 1024;
 constexpr int kNW = kNT / 64;
-constexpr double kTwoPi = 6.283185307179586476925286766559;
 
 // d = log phi - log psi of walker i; false when any of the four floats is not finite
 __device__ __forceinline__ bool fid_d(const float* __restrict__ lpsi, const float* __restrict__ lphi, int i,
@@ -38,11 +36,9 @@ __device__ __forceinline__ bool fid_d(const float* __restrict__ lpsi, const floa
 
 // z = e^{dr - m} (cos di, sin di)
 __device__ __forceinline__ void fid_term(double dr, double di, double m, double& zr, double& zi) {
-  const double e = exp(dr - m);
-  double s, c;
-  sincos(remainder(di, kTwoPi), &s, &c);
-  zr = e * c;
-  zi = e * s;
+  const double2 z = amp_ratio(dr - m, di);
+  zr = z.x;
+  zi = z.y;
 }
 
 // a b + c d with each product and the sum rounded on its own (the compiler's default would
@@ -85,8 +81,7 @@ __global__ __launch_bounds__(kNT) void fidelity_partial_kernel(const float* __re
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    double v = acc[q];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const double v = wave_sum(acc[q]);
     if (lane == 0) wsum[w][q] = v;
   }
   __syncthreads();

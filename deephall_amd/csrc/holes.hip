@@ -9,18 +9,15 @@
 //
 //   ratios  one thread per walker: the walker is valid when its 2 K log entries and its K ratios
 //           are finite; r into the workspace as ratio[c][b] (NaN for an invalid walker), valid[b].
-//   sums    one workgroup per (c, c'), and one more for the count: each thread its strided walkers
-//           in order, a wave by xor shuffles, the waves in order.
-// All in double, a fixed order and no float atomics: two calls give identical bits.
+//   sums    one workgroup per (c, c'), and one more for the count, by block_sum.
+// The estimators' convention (estimator_common.h): two calls give identical bits.
 #include "dh_internal.h"
-#include "device_common.h"
+#include "estimator_common.h"
 
 namespace dh {
 namespace {
 
 constexpr int kSumNT = 256;
-constexpr int kSumNW = kSumNT / 64;
-constexpr double kTwoPi = 6.283185307179586476925286766559;
 
 __global__ __launch_bounds__(256) void hole_ratio_kernel(const double2* __restrict__ L, int B, int K,
                                                          const double* __restrict__ shift,
@@ -33,12 +30,9 @@ __global__ __launch_bounds__(256) void hole_ratio_kernel(const double2* __restri
   for (int c = 0; c < K; ++c) ok = ok && isfinite(row[c].x) && isfinite(row[c].y);
   // an overflowing ratio would poison the sums: its walker is dropped with the rest
   for (int c = 0; c < K; ++c) ok = ok && isfinite(exp(row[c].x - l0.x - shift[c]));
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   for (int c = 0; c < K; ++c) {
-    const double m = exp(row[c].x - l0.x - shift[c]);
-    double s, co;
-    sincos(remainder(row[c].y - l0.y, kTwoPi), &s, &co);
-    ratio[(size_t)c * B + b] = ok ? make_double2(m * co, m * s) : make_double2(nan, nan);
+    const double2 r = amp_ratio(row[c].x - l0.x - shift[c], row[c].y - l0.y);
+    ratio[(size_t)c * B + b] = ok ? r : make_double2(quiet_nan(), quiet_nan());
   }
   valid[b] = ok ? 1 : 0;
 }
@@ -47,44 +41,25 @@ __global__ __launch_bounds__(256) void hole_ratio_kernel(const double2* __restri
 __global__ __launch_bounds__(kSumNT) void hole_sum_kernel(const double2* __restrict__ ratio,
                                                           const int32_t* __restrict__ valid, int B, int K,
                                                           double2* __restrict__ S, int32_t* __restrict__ nvalid) {
-  __shared__ double wsum[kSumNW][2];
-  __shared__ int wcnt[kSumNW];
-  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int q = blockIdx.x, tid = threadIdx.x;
   const bool count = q == K * K;
   const double2* ra = ratio + (size_t)(count ? 0 : q / K) * B;
   const double2* rb = ratio + (size_t)(count ? 0 : q % K) * B;
-  double sr = 0.0, si = 0.0;
+  double sum[2] = {0.0, 0.0};
   int cnt = 0;
   for (int b = tid; b < B; b += kSumNT) {
     if (!valid[b]) continue;
     const double2 u = ra[b], v = rb[b];
-    sr += u.x * v.x + u.y * v.y;  // conj(u) v
-    si += u.x * v.y - u.y * v.x;
+    sum[0] += u.x * v.x + u.y * v.y;  // conj(u) v
+    sum[1] += u.x * v.y - u.y * v.x;
     ++cnt;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    sr += __shfl_xor(sr, off, 64);
-    si += __shfl_xor(si, off, 64);
-    cnt += __shfl_xor(cnt, off, 64);
-  }
-  if (lane == 0) {
-    wsum[w][0] = sr;
-    wsum[w][1] = si;
-    wcnt[w] = cnt;
-  }
-  __syncthreads();
+  block_sum<kSumNT>(sum, cnt);
   if (tid == 0) {
-    double tr = 0.0, ti = 0.0;
-    int n = 0;
-    for (int j = 0; j < kSumNW; ++j) {
-      tr += wsum[j][0];
-      ti += wsum[j][1];
-      n += wcnt[j];
-    }
     if (count)
-      *nvalid = n;
+      *nvalid = cnt;
     else
-      S[q] = make_double2(tr, ti);
+      S[q] = make_double2(sum[0], sum[1]);
   }
 }
 

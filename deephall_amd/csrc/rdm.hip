@@ -38,7 +38,7 @@
 #include <vector>
 
 #include "dh_internal.h"
-#include "device_common.h"
+#include "estimator_common.h"
 
 namespace dh {
 namespace {
@@ -49,8 +49,6 @@ constexpr int kRdmMaxN = 32;
 constexpr int kTile = 32;                // pass 2: rho tile edge
 constexpr int kStage = 16;               // pass 2: samples per LDS stage
 constexpr int kMaxSplit = 16;
-constexpr double kTwoPi = 6.283185307179586476925286766559;
-constexpr double kFourPi = 12.566370614359172953850573533118;
 
 __host__ __device__ inline int level_offset(int flux, int n) { return n * (flux + 1) + n * (n - 1); }
 
@@ -147,13 +145,11 @@ __global__ __launch_bounds__(256) void rdm_uv_kernel(const float* __restrict__ x
     const float* lp = logpsi + 2 * (size_t)b;
     const float* lq = logpsi_p + ((size_t)smp * N + a) * 2;
     const double dr = (double)lq[0] - (double)lp[0], di = (double)lq[1] - (double)lp[1];
-    const double m = exp(dr);
-    double s, c;
-    sincos(remainder(di, kTwoPi), &s, &c);
-    ratio[sl][a][0] = m * c;
-    ratio[sl][a][1] = m * s;
+    const double2 r = amp_ratio(dr, di);
+    ratio[sl][a][0] = r.x;
+    ratio[sl][a][1] = r.y;
     // all of this sample's log-amplitudes pass here: log psi by every a, log psi(R_a') by its own
-    if (!(isfinite(lp[0]) && isfinite(lp[1]) && isfinite(lq[0]) && isfinite(lq[1]) && isfinite(m))) ok[sl] = 0;
+    if (!(isfinite(lp[0]) && isfinite(lp[1]) && isfinite(lq[0]) && isfinite(lq[1]) && isfinite(exp(dr)))) ok[sl] = 0;
   }
   __syncthreads();
   if (tid < kRdmSmp && smp0 + tid < samples && ok[tid]) atomicAdd(nvalid, 1);

@@ -38,7 +38,7 @@
 // instantiation rounds alike: two calls give identical bits, and the pair sums are the same bits
 // with and without the multipoles.
 #include "dh_internal.h"
-#include "device_common.h"
+#include "estimator_common.h"
 
 namespace dh {
 namespace {
@@ -63,11 +63,6 @@ __device__ __forceinline__ Smem carve(double* base, int nlm) {
   m.ainv = m.a + n2;
   m.acc = reinterpret_cast<double2*>(m.ainv + n2);
   return m;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 template <bool WANT>
@@ -149,9 +144,9 @@ __device__ __forceinline__ void walker_pairs_c(int N, int n_up, int lmax, int la
       pm[k] = pc[k];
       pc[k] = pn;
     }
-    t0 = wave_sum_d(t0);
-    t1 = wave_sum_d(t1);
-    t2 = wave_sum_d(t2);
+    t0 = wave_sum(t0);
+    t1 = wave_sum(t1);
+    t2 = wave_sum(t2);
     if (L < 64) {
       if (lane == L) {
         lo[0] += t0;
@@ -252,7 +247,7 @@ __global__ __launch_bounds__(64) void sf_pairs_kernel(const float* __restrict__ 
   const int lane = threadIdx.x, nl = lmax + 1;
   const Smem m = carve(sf_smem, 0);
   fill_tables<false>(m, lmax, lane);
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double nan = quiet_nan();
   for (size_t b = blockIdx.x; b < (size_t)B; b += gridDim.x) {
     double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {0.0, 0.0, 0.0};
     const bool ok = load_walker(x, b, N, lane, m);
@@ -271,7 +266,7 @@ __global__ __launch_bounds__(64) void sf_multipoles_kernel(const float* __restri
   const int lane = threadIdx.x;
   const Smem m = carve(sf_smem, nlm);
   fill_tables<true>(m, lmax, lane);
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double nan = quiet_nan();
   for (size_t b = blockIdx.x; b < (size_t)B; b += gridDim.x) {
     zero_acc(m, nlm, lane);
     const bool ok = load_walker(x, b, N, lane, m);

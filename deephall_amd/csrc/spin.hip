@@ -9,28 +9,24 @@
 //
 //   exchange  one thread per float2 of xs[(pair1 - pair0) B][N]: row (p - pair0) B + b is walker b
 //             with slots i and j of pair p exchanged.  Coordinates are copied, never recomputed.
-//   ratios    one thread per (p, b) of a window: exp(log psi(R_p) - log psi(R)) in double from the
-//             float32 logs (the phase folded into [-pi, pi] first) into ratio[p][b], the
-//             workspace; a non-finite log or ratio is stored as NaN.  Elementwise: what a pair
-//             stores does not depend on the window it arrived in.
+//   ratios    one thread per (p, b) of a window: amp_ratio of log psi(R_p) - log psi(R) into
+//             ratio[p][b], the workspace; a non-finite log or ratio is stored as NaN.
+//             Elementwise: what a pair stores does not depend on the window it arrived in.
 //   walker    after every pair has been stored, one thread per walker: the walker is valid when
 //             its own log and its P ratios are finite; s2[b] = S^2_loc with the pairs added in
 //             ascending p, NaN for an invalid walker; valid[b] to the workspace.
 //   sums      one workgroup per pair, and one more for the total: the sum over the valid walkers
-//             of ratio[p][b] (of s2[b], with nvalid as an integer count), each thread its strided
-//             walkers in order, a wave by xor shuffles, the waves in order.
-// All in double, a fixed order and no float atomics: two calls give identical bits, and so do one
+//             of ratio[p][b] (of s2[b], with nvalid as an integer count) by block_sum.
+// The estimators' convention (estimator_common.h): two calls give identical bits, and so do one
 // window of all pairs and one window per pair.  P = 0 (one species empty) launches neither
 // exchange nor ratios, and S^2_loc = (N / 2)(N / 2 + 1) exactly.
 #include "dh_internal.h"
-#include "device_common.h"
+#include "estimator_common.h"
 
 namespace dh {
 namespace {
 
 constexpr int kSumNT = 256;
-constexpr int kSumNW = kSumNT / 64;
-constexpr double kTwoPi = 6.283185307179586476925286766559;
 
 __global__ __launch_bounds__(256) void spin_exchange_kernel(const float2* __restrict__ x, int B, int N, int n_up,
                                                             int n_dn, int pair0, size_t total,
@@ -55,12 +51,10 @@ __global__ __launch_bounds__(256) void spin_ratio_kernel(const float* __restrict
   const float* l0 = lp + 2 * b;
   const float* l1 = lps + 2 * idx;
   const double dr = (double)l1[0] - (double)l0[0], di = (double)l1[1] - (double)l0[1];
-  const double m = exp(dr);
-  double s, c;
-  sincos(remainder(di, kTwoPi), &s, &c);
-  const double re = m * c, im = m * s;
+  const double2 r = amp_ratio(dr, di);
+  const double re = r.x, im = r.y;
   const bool ok = isfinite(l0[0]) && isfinite(l0[1]) && isfinite(l1[0]) && isfinite(l1[1]) && isfinite(re) && isfinite(im);
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double nan = quiet_nan();
   ratio[(size_t)pair0 * B + idx] = ok ? make_double2(re, im) : make_double2(nan, nan);
 }
 
@@ -77,8 +71,7 @@ __global__ __launch_bounds__(256) void spin_walker_kernel(const float* __restric
     sr += r.x;
     si += r.y;
   }
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  s2[b] = ok ? make_double2(c0 - sr, -si) : make_double2(nan, nan);
+  s2[b] = ok ? make_double2(c0 - sr, -si) : make_double2(quiet_nan(), quiet_nan());
   valid[b] = ok ? 1 : 0;
 }
 
@@ -88,43 +81,24 @@ __global__ __launch_bounds__(kSumNT) void spin_sum_kernel(const double2* __restr
                                                           const int32_t* __restrict__ valid, int B, int P,
                                                           double2* __restrict__ pairs, double2* __restrict__ total,
                                                           int32_t* __restrict__ nvalid) {
-  __shared__ double wsum[kSumNW][2];
-  __shared__ int wcnt[kSumNW];
-  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int p = blockIdx.x, tid = threadIdx.x;
   const double2* src = p < P ? ratio + (size_t)p * B : s2;
-  double sr = 0.0, si = 0.0;
+  double sum[2] = {0.0, 0.0};
   int cnt = 0;
   for (int b = tid; b < B; b += kSumNT) {
     if (!valid[b]) continue;
     const double2 v = src[b];
-    sr += v.x;
-    si += v.y;
+    sum[0] += v.x;
+    sum[1] += v.y;
     ++cnt;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    sr += __shfl_xor(sr, off, 64);
-    si += __shfl_xor(si, off, 64);
-    cnt += __shfl_xor(cnt, off, 64);
-  }
-  if (lane == 0) {
-    wsum[w][0] = sr;
-    wsum[w][1] = si;
-    wcnt[w] = cnt;
-  }
-  __syncthreads();
+  block_sum<kSumNT>(sum, cnt);
   if (tid == 0) {
-    double tr = 0.0, ti = 0.0;
-    int n = 0;
-    for (int j = 0; j < kSumNW; ++j) {
-      tr += wsum[j][0];
-      ti += wsum[j][1];
-      n += wcnt[j];
-    }
     if (p < P) {
-      pairs[p] = make_double2(tr, ti);
+      pairs[p] = make_double2(sum[0], sum[1]);
     } else {
-      *total = make_double2(tr, ti);
-      *nvalid = n;
+      *total = make_double2(sum[0], sum[1]);
+      *nvalid = cnt;
     }
   }
 }

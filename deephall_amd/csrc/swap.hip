@@ -19,17 +19,17 @@
 //             Coordinates are copied, never recomputed.
 //   reduce    sums[a][k] = sum over the matched pairs of angle a in sector k of
 //             exp(log psi(R1') + log psi(R2') - log psi(R1) - log psi(R2)), complex, in double from
-//             the float32 logs on.  One workgroup per (a, k) walks the rows of angle a in a fixed
-//             order — each thread its strided rows in order, a wave by xor shuffles, the waves in
-//             order — so two calls give identical bits; no float atomics.  An (a, k) without a
-//             matched pair writes zeros.
+//             the float32 logs on (amp_ratio).  One workgroup per (a, k) walks the rows of angle a:
+//             each thread its strided rows in order, a wave by xor shuffles, then thread q adds
+//             component q of the waves in order (the estimators' convention, estimator_common.h).
+//             An (a, k) without a matched pair writes zeros.
 //
 // Only about 40 % of the pairs match, and every row that reaches dh_logpsi costs a
 // full forward pass: hence the compaction between classify and the wavefunction call.
 // Every grid below has at least one block whenever B >= 2 and A >= 1, which the C entry points
 // check first; M = 0 and an angle without matches need no launch of their own.
 #include "dh_internal.h"
-#include "device_common.h"
+#include "estimator_common.h"
 
 namespace dh {
 namespace {
@@ -38,7 +38,6 @@ constexpr int kScanNT = 1024;
 constexpr int kScanNW = kScanNT / 64;
 constexpr int kRedNT = 256;
 constexpr int kRedNW = kRedNT / 64;
-constexpr double kTwoPi = 6.283185307179586476925286766559;
 
 // the number of slots [lo, hi) of walker xb inside the cap theta < th
 __device__ __forceinline__ int count_in(const float* __restrict__ xb, int lo, int hi, float th) {
@@ -144,11 +143,9 @@ __global__ __launch_bounds__(kRedNT) void swap_reduce_kernel(const float* __rest
     const float* s1 = lps + 4 * (size_t)o;  // rows 2 o and 2 o + 1
     const double dr = ((double)s1[0] + (double)s1[2]) - ((double)l1[0] + (double)l2[0]);
     const double di = ((double)s1[1] + (double)s1[3]) - ((double)l1[1] + (double)l2[1]);
-    const double e = exp(dr);
-    double s, c;
-    sincos(remainder(di, kTwoPi), &s, &c);
-    sr += e * c;
-    si += e * s;
+    const double2 r = amp_ratio(dr, di);
+    sr += r.x;
+    si += r.y;
   }
   for (int off = 32; off > 0; off >>= 1) {
     sr += __shfl_xor(sr, off, 64);
