@@ -5,6 +5,7 @@ Public names mirror the reference package:
   make_network           deephall.networks.make_network
   local_energy           deephall.hamiltonian.local_energy   (alias make_local_energy)
   make_local_kinetic_energy, make_potential
+  make_external_potential             the one-body impurity term (not in the reference)
   make_mcmc_step, update_mcmc_width   deephall.mcmc
   make_loss_fn, LossMode              deephall.loss (statistics + parameter gradient)
   make_optimizer_step                 deephall.optimizers (KFAC = the default, Adam, none)
@@ -12,8 +13,9 @@ Public names mirror the reference package:
 All compute runs in the HIP library deephall_amd/_lib/libdeephall_amd.so.
 """
 
-from .config import MCMC, Config, InteractionType, Network, NetworkType, OrbitalType, PsiformerNetwork, System
-from .hamiltonian import local_energy, make_local_energy, make_local_kinetic_energy, make_potential
+from .config import MCMC, Config, Impurity, InteractionType, Network, NetworkType, OrbitalType, PsiformerNetwork, System
+from .hamiltonian import (local_energy, make_external_potential, make_local_energy, make_local_kinetic_energy,
+                          make_potential)
 from .loss import LossMode, make_loss_fn
 from .mcmc import make_mcmc_step, update_mcmc_width
 from .networks import make_network
@@ -35,6 +37,8 @@ __all__ = [
     "make_local_energy",
     "make_local_kinetic_energy",
     "make_potential",
+    "make_external_potential",
+    "Impurity",
     "make_mcmc_step",
     "update_mcmc_width",
     "make_loss_fn",

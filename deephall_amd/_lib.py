@@ -120,12 +120,20 @@ EXPORTS = [
     "dh_hole_workspace_bytes",
     "dh_hole_logs",
     "dh_hole_gram",
+    "dh_impurity_check",
+    "dh_external_potential",
+    "dh_axis_histogram",
 ]
 
 DH_QUASIHOLE_MAX_HOLES = 8
 DH_HOLE_MAX_CONFIGS = 16
 QUASIHOLE_BASES = {"halperin": 0, "pfaffian": 1}  # DH_QUASIHOLE_*
 HOLE_KINDS = {"both": 0, "up": 1, "down": 2, "A": 3, "B": 4}  # DH_HOLE_*
+
+DH_MAX_IMPURITIES = 8
+IMPURITY_KINDS = {"gaussian": 0, "charge": 1}  # DH_IMPURITY_*
+IMPURITY_SPECIES = {"both": 0, "up": 1, "down": 2}  # DH_HOLE_BOTH, DH_HOLE_UP, DH_HOLE_DOWN
+DH_AXIS_MAX_BINS = 4096
 
 DH_SWAP_MAX_ANGLES = 64
 DH_RDM_MAX_LEVELS = 4
@@ -197,6 +205,17 @@ class DhHoleConfigs(C.Structure):
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
         self.struct_size = C.sizeof(DhHoleConfigs)
+
+
+class DhImpurity(C.Structure):
+    _fields_ = [
+        ("theta", C.c_double),
+        ("phi", C.c_double),
+        ("strength", C.c_double),
+        ("width", C.c_double),
+        ("kind", C.c_int),
+        ("species", C.c_int),
+    ]
 
 
 _lib = None
@@ -356,6 +375,13 @@ def load(path: Path | str | None = None):
     lib.dh_hole_logs.restype = i32
     lib.dh_hole_gram.argtypes = [vp, i32, i32, vp, vp, vp, vp, sz, vp]
     lib.dh_hole_gram.restype = i32
+    pi = C.POINTER(DhImpurity)  # the impurities: a host array
+    lib.dh_impurity_check.argtypes = [pi, i32]
+    lib.dh_impurity_check.restype = i32
+    lib.dh_external_potential.argtypes = [vp, i32, i32, i32, C.c_double, pi, i32, vp, vp, vp]
+    lib.dh_external_potential.restype = i32
+    lib.dh_axis_histogram.argtypes = [vp, i32, i32, i32, C.c_double, C.c_double, i32, vp, vp]
+    lib.dh_axis_histogram.restype = i32
     lib.dh_spin_workspace_bytes.argtypes = [i32, i32, i32]
     lib.dh_spin_workspace_bytes.restype = sz
     lib.dh_spin_exchange.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp]

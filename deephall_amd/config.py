@@ -53,6 +53,57 @@ class OrbitalType(str, enum.Enum):
     sparse = "sparse"
 
 
+IMPURITY_KINDS = ("gaussian", "charge")
+IMPURITY_SPECIES = ("both", "up", "down")
+MAX_IMPURITIES = 8
+
+
+@dataclass(frozen=True)
+class Impurity:
+    """A local one-body potential pinned at (theta, phi) (not in the reference; csrc/impurity.hip).
+    With R the sphere's radius and c^2 = 2 R^2 (1 - cos gamma) the squared chord to an electron,
+    ``kind`` "gaussian": strength exp(-c^2 / (2 width^2)); "charge": strength / sqrt(c^2 + width^2),
+    a point charge at the height ``width`` above the surface.  ``width`` is in magnetic lengths, the
+    unit of ``System.radius``, and > 0.  ``strength`` > 0 repels the electrons (pins a quasihole).
+    ``species``: "both", "up" or "down", the words of ``network.quasihole.species``."""
+
+    theta: float
+    phi: float
+    strength: float
+    kind: str = "gaussian"
+    width: float = 1.0
+    species: str = "both"
+
+    def __post_init__(self):
+        for name in ("theta", "phi", "strength", "width"):
+            object.__setattr__(self, name, float(getattr(self, name)))
+        for name in ("kind", "species"):
+            v = getattr(self, name)
+            object.__setattr__(self, name, str(getattr(v, "value", v)))
+        if self.kind not in IMPURITY_KINDS:
+            raise ValueError(f"impurity: kind {self.kind!r} is not one of {IMPURITY_KINDS}")
+        if self.species not in IMPURITY_SPECIES:
+            raise ValueError(f"impurity: species {self.species!r} is not one of {IMPURITY_SPECIES}")
+        if not self.width > 0.0:
+            raise ValueError(f"impurity: width must be > 0, got {self.width}")
+
+
+def as_impurities(entries) -> tuple:
+    """A tuple of `Impurity` from Impurity objects, dicts of its fields or sequences in field order
+    (theta, phi, strength[, kind, width, species]): what a config file can hold."""
+    out = []
+    for e in entries or ():
+        if isinstance(e, Impurity):
+            out.append(e)
+        elif isinstance(e, dict):
+            out.append(Impurity(**e))
+        else:
+            out.append(Impurity(*e))
+    if len(out) > MAX_IMPURITIES:
+        raise ValueError(f"impurity: at most {MAX_IMPURITIES} impurities, got {len(out)}")
+    return tuple(out)
+
+
 @dataclass
 class System:
     flux: int = 2
@@ -63,6 +114,10 @@ class System:
     lz_penalty: float = 0.0
     l2_penalty: float = 0.0
     interaction_type: InteractionType = InteractionType.coulomb
+    impurities: tuple = ()  # of Impurity; not in the reference
+
+    def __post_init__(self):
+        self.impurities = as_impurities(self.impurities)  # lists or dicts from a config file
 
 
 @dataclass

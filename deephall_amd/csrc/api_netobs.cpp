@@ -1,6 +1,9 @@
 // The estimator calls of the C ABI (include/deephall_amd.h) that take no handle: they see walkers
-// and log psi values only.  Histograms, monopole orbitals, dh_swap_*, dh_rdm_*, dh_spin_*, dh_sf_*
-// and the hole overlap matrix.  Every check comes before any device call.
+// and log psi values only.  Histograms, monopole orbitals, dh_swap_*, dh_rdm_*, dh_spin_*, dh_sf_*,
+// the hole overlap matrix, and the impurity potential with its axis histogram.  Every check comes
+// before any device call.
+#include <cmath>
+
 #include "api_internal.h"
 
 using namespace dh;
@@ -255,6 +258,74 @@ int dh_hole_gram(const double* L, int B, int n_configs, const double* shift, dou
   if (workspace_bytes < dh_hole_workspace_bytes(B, n_configs))
     return fail(DH_ENOMEM, "Holes: workspace smaller than dh_hole_workspace_bytes");
   launch_hole_gram(L, B, n_configs, shift, S, nvalid, workspace, (hipStream_t)stream);
+  return check_launch();
+}
+
+// ---- impurity potential and the density around an axis (impurity.hip) ----
+
+namespace {
+const double kPi = 3.14159265358979323846;
+const char* impurity_error(const dh_impurity* imp, int n) {
+  if (n < 0 || n > DH_MAX_IMPURITIES) return "impurity: n_imp outside 0..DH_MAX_IMPURITIES";
+  if (n > 0 && !imp) return "impurity: null array";
+  for (int a = 0; a < n; ++a) {
+    const dh_impurity& m = imp[a];
+    if (!std::isfinite(m.theta) || !std::isfinite(m.phi) || !std::isfinite(m.strength) || !std::isfinite(m.width))
+      return "impurity: a field is not finite";
+    if (!(m.width > 0.0)) return "impurity: width <= 0";
+    if (m.kind != DH_IMPURITY_GAUSSIAN && m.kind != DH_IMPURITY_CHARGE) return "impurity: unknown kind";
+    if (m.species != DH_HOLE_BOTH && m.species != DH_HOLE_UP && m.species != DH_HOLE_DOWN)
+      return "impurity: unknown species";
+    if (m.theta < 0.0 || m.theta > kPi) return "impurity: theta outside [0, pi]";
+  }
+  return nullptr;
+}
+const char* impurity_size_error(int B, int n_up, int n_dn) {
+  if (B < 1) return "impurity: B < 1";
+  if (n_up < 0 || n_dn < 0 || n_up > 32 || n_dn > 32 || n_up + n_dn < 1 || n_up + n_dn > 32)
+    return "impurity: n_up, n_dn < 0 or n_up + n_dn outside 1..32";
+  if ((int64_t)B * (n_up + n_dn) > INT32_MAX) return "impurity: B nelec >= 2^31";
+  return nullptr;
+}
+}  // namespace
+
+int dh_impurity_check(const dh_impurity* impurities, int n_imp) {
+  if (const char* e = impurity_error(impurities, n_imp)) return fail(DH_EINVAL, e);
+  return DH_OK;
+}
+
+int dh_external_potential(const float* x, int B, int n_up, int n_dn, double radius, const dh_impurity* impurities,
+                          int n_imp, float* e_l, float* ext, void* stream) {
+  if (!x || !ext) return fail(DH_EINVAL, "impurity: null pointer");
+  if (const char* e = impurity_size_error(B, n_up, n_dn)) return fail(DH_EINVAL, e);
+  if (!std::isfinite(radius) || !(radius > 0.0)) return fail(DH_EINVAL, "impurity: radius not finite or <= 0");
+  if (const char* e = impurity_error(impurities, n_imp)) return fail(DH_EINVAL, e);
+  ImpurityTable tab{};
+  tab.n = n_imp;
+  for (int a = 0; a < n_imp; ++a) {
+    const dh_impurity& m = impurities[a];
+    double v[3];
+    impurity_vector(m.theta, m.phi, v);
+    tab.ax[a] = v[0], tab.ay[a] = v[1], tab.az[a] = v[2];
+    tab.strength[a] = m.strength;
+    const bool g = m.kind == DH_IMPURITY_GAUSSIAN;
+    tab.p[a] = g ? (radius / m.width) * (radius / m.width) : 2.0 * radius * radius;
+    tab.q[a] = g ? 0.0 : m.width * m.width;
+    tab.kind[a] = g ? kImpurityGaussian : kImpurityCharge;
+    tab.species[a] = m.species;
+  }
+  launch_external_potential(x, B, n_up + n_dn, n_up, tab, e_l, ext, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_axis_histogram(const float* x, int B, int n_up, int n_dn, double axis_theta, double axis_phi, int bins,
+                      unsigned* counts, void* stream) {
+  if (!x || !counts) return fail(DH_EINVAL, "impurity: null pointer");
+  if (const char* e = impurity_size_error(B, n_up, n_dn)) return fail(DH_EINVAL, e);
+  if (!std::isfinite(axis_theta) || !std::isfinite(axis_phi)) return fail(DH_EINVAL, "impurity: axis not finite");
+  if (axis_theta < 0.0 || axis_theta > kPi) return fail(DH_EINVAL, "impurity: axis_theta outside [0, pi]");
+  if (bins < 1 || bins > 4096) return fail(DH_EINVAL, "impurity: bins outside 1..4096");
+  launch_axis_histogram(x, B, n_up + n_dn, n_up, axis_theta, axis_phi, bins, counts, (hipStream_t)stream);
   return check_launch();
 }
 

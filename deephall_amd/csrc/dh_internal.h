@@ -536,6 +536,26 @@ size_t hole_workspace_bytes(int B, int K);
 void launch_hole_gram(const double* L, int B, int K, const double* shift, double* S, int32_t* nvalid, void* workspace,
                       hipStream_t s);
 
+// impurity.hip: the one-body impurity term of the local energy (dh_external_potential) and the
+// histogram of the angle from an axis (dh_axis_histogram).  The table is a kernel argument: unit
+// vectors and coefficients from the host, in double.  p, q: R^2 / w^2 and 0 (gaussian), 2 R^2 and
+// h^2 (charge).  The limits (1 <= N <= 32, B >= 1, B N < 2^31, n <= kMaxImpurities, 1 <= bins <=
+// 4096) are the callers' to check.
+constexpr int kMaxImpurities = 8;
+enum { kImpurityGaussian = 0, kImpurityCharge = 1 };
+enum { kImpurityBoth = 0, kImpurityUp = 1, kImpurityDown = 2 };  // = DH_HOLE_BOTH, DH_HOLE_UP, DH_HOLE_DOWN
+struct ImpurityTable {
+  double ax[kMaxImpurities], ay[kMaxImpurities], az[kMaxImpurities];
+  double strength[kMaxImpurities], p[kMaxImpurities], q[kMaxImpurities];
+  int kind[kMaxImpurities], species[kMaxImpurities];
+  int n;
+};
+void impurity_vector(double theta, double phi, double* v);  // (sin th cos ph, sin th sin ph, cos th)
+void launch_external_potential(const float* x, int B, int N, int n_up, const ImpurityTable& tab, float* e_l,
+                               float* ext, hipStream_t s);
+void launch_axis_histogram(const float* x, int B, int N, int n_up, double axis_theta, double axis_phi, int bins,
+                           unsigned* counts, hipStream_t s);
+
 // det.hip: backward of log psi = J + log sum_k det Phi_k for per-walker cotangents ct[nw][2]:
 // dF [nw*N][ld_orb] (all columns written) and jg[nw][2] = ct.re * dJ / d(ee_par, ee_anti)
 void launch_det_bwd(const Dims& d, const float* F, const float* x, const float* jastrow, const float* norm,

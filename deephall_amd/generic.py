@@ -94,18 +94,24 @@ def make_local_kinetic_energy(f, Q: float, r, chunk_size: int | None = None):
 
 def local_energy(f, system, chunk_size: int | None = None):
     """hamiltonian.py:175-212 for any per-walker ``f``: ``_e_l(params, data[B, N, 2])``."""
-    from .hamiltonian import make_potential
+    from .hamiltonian import make_external_potential, make_potential
 
     Q = system.flux / 2
     r = float(system.radius) if system.radius is not None else Q**0.5
     ke = make_local_kinetic_energy(f, Q, r, chunk_size)
     pe = make_potential(system.interaction_type, Q, r)
     strength = float(system.interaction_strength)
+    impurities = tuple(getattr(system, "impurities", ()) or ())
+    ext = make_external_potential(impurities, system.nspins, r) if impurities else None
 
     def _e_l(params, data: torch.Tensor):
         potential = pe(data) * strength
         kinetic, moms = ke(params, data)
-        return kinetic + potential, dict(moms, potential=potential, kinetic=kinetic)
+        out = dict(moms, potential=potential, kinetic=kinetic)
+        if ext is None:
+            return kinetic + potential, out
+        out["external"] = ext(data)  # the impurity term (dh_external_potential), as the native route adds it
+        return kinetic + potential + out["external"], out
 
     return _e_l
 

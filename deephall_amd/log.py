@@ -94,7 +94,7 @@ def _plain(obj):
     if isinstance(obj, enum.Enum):
         return obj.value
     if isinstance(obj, tuple):
-        return list(obj)
+        return [_plain(v) for v in obj]
     return obj
 
 

@@ -27,6 +27,10 @@ with the same names, options, value/state keys and digests:
   not in the reference): log psi of K hole configurations on the same walkers in double and the
   K x K Gram matrix of their ratios are csrc/quasihole.hip and csrc/holes.hip (``dh_hole_*``);
   holonomy.py turns the overlaps into Berry phases and non-Abelian holonomies on the host;
+* the density around any axis and the excess charge inside a cap about it
+  (observables/axis_density.py, not in the reference): equal-area bins of r_i . a, integer counts by
+  species in csrc/impurity.hip (``dh_axis_histogram``); the axis can be one of ``system.impurities``,
+  whose potential the adaptor's potential energy includes (``dh_external_potential``);
 * every wavefunction value goes through ``dh_logpsi`` (Psiformer or the native Laughlin
   state), the walk through ``dh_mcmc_step``;
 * ``evaluate`` is a minimal stand-in for NetObs's own evaluation loop (restore, burn-in,
@@ -38,8 +42,8 @@ with the same names, options, value/state keys and digests:
 from .adaptor import DeepHallAdaptor, DeepHallAuxData
 from .estimator import Estimator, Observable, evaluate
 from .hall_system import HallSystem
-from .observables import (density, hole_overlap, ll_rdm, one_rdm, overlap, pair_corr, renyi2, spin_square,
-                          structure_factor)
+from .observables import (axis_density, density, hole_overlap, ll_rdm, one_rdm, overlap, pair_corr, renyi2,
+                          spin_square, structure_factor)
 
 
 class _Registry(dict):
@@ -70,6 +74,7 @@ EXTRA_ESTIMATORS = _Registry({
     "spin_square": spin_square.DEFAULT,
     "structure_factor": structure_factor.DEFAULT,
     "hole_overlap": hole_overlap.DEFAULT,
+    "axis_density": axis_density.DEFAULT,
 })
 
 # The own keys are the reference's ``deephall@`` names, so the registry still lists exactly what

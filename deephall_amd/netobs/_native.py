@@ -329,6 +329,23 @@ def sf_accumulate_host(x: torch.Tensor, n_up: int, lmax: int, multipoles: bool =
     return _sf_unpack(out.cpu(), nl, nlm, multipoles)
 
 
+# ---- density around an axis (csrc/impurity.hip) ----------------------------------------------------
+
+def axis_histogram(x: torch.Tensor, nspins, axis, bins: int) -> torch.Tensor:
+    """counts[2, bins] int64 on the device: the up (row 0) and down (row 1) electrons of walkers
+    x[B, N, 2] by the cosine u of their angle from ``axis`` = (theta, phi), in ``bins`` bins of equal
+    area, bin k being 1 - 2 (k + 1) / bins < u <= 1 - 2 k / bins.  Non-finite coordinates are dropped."""
+    x = _check_cuda(x)
+    B, N, _ = x.shape
+    n_up, n_dn = int(nspins[0]), int(nspins[1])
+    if n_up + n_dn != N:
+        raise ValueError(f"axis_histogram: walkers of {N} electrons, nspins = {(n_up, n_dn)}")
+    counts = torch.zeros(2, max(int(bins), 1), dtype=torch.int32, device=x.device)  # the kernel's unsigned
+    _lib.check(_lib.load().dh_axis_histogram(_ptr(x), B, n_up, n_dn, float(axis[0]), float(axis[1]), int(bins),
+                                             _ptr(counts), _stream(x.device)))
+    return counts.long() & 0xFFFFFFFF
+
+
 # ---- quasihole overlap matrix (csrc/quasihole.hip hole_logs_kernel, csrc/holes.hip) ---------------
 
 class HoleTable:

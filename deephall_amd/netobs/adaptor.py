@@ -3,7 +3,8 @@
 ``restore`` reads ``config.yml`` beside the checkpoint (our LogManager's format: a
 ``git_commit`` line, then the Config), builds the network, and restores parameters,
 this rank's walkers and the MCMC width (log.py restore_checkpoint).  The walking step is
-``dh_mcmc_step``; the energies are ``dh_local_energy`` (kinetic) and ``dh_potential``.
+``dh_mcmc_step``; the energies are ``dh_local_energy`` (kinetic), ``dh_potential`` and, with
+``system.impurities``, ``dh_external_potential`` (the potential energy is their sum).
 """
 
 from __future__ import annotations
@@ -15,7 +16,7 @@ from typing import Any, TypedDict
 import torch
 
 from ..config import Config
-from ..hamiltonian import make_local_kinetic_energy, make_potential
+from ..hamiltonian import make_external_potential, make_local_kinetic_energy, make_potential
 from ..log import LogManager
 from ..mcmc import make_mcmc_step
 from ..networks import make_network
@@ -49,6 +50,8 @@ class DeepHallAdaptor:
         radius = float(cfg.system.radius or math.sqrt(Q))
         self.kinetic_energy = make_local_kinetic_energy(model, Q, radius)
         self.potential_energy = make_potential(cfg.system.interaction_type, Q, radius)
+        self.external_energy = (make_external_potential(cfg.system.impurities, cfg.system.nspins, radius)
+                                if cfg.system.impurities else None)
         _, state = LogManager.restore_checkpoint(ckpt_path, model, device)
         self.batch_per_device = state.data.shape[0]
         system = HallSystem(spins=list(cfg.system.nspins), ndim=2, flux=cfg.system.flux)
@@ -80,7 +83,8 @@ class DeepHallAdaptor:
 
     def call_local_potential_energy(self, params, key, electrons, system=None):
         del params, key, system
-        return self.potential_energy(electrons) * self.cfg.system.interaction_strength
+        pair = self.potential_energy(electrons) * self.cfg.system.interaction_strength
+        return pair if self.external_energy is None else pair + self.external_energy(electrons)
 
 
 DEFAULT = DeepHallAdaptor

@@ -21,20 +21,13 @@ from __future__ import annotations
 import torch
 
 from .. import _lib
-from .psiformer import NetworkSpec, ParamTree, Psiformer, _ptr, _stream, get_handle
+from .psiformer import NetworkSpec, ParamTree, Psiformer, _ptr, _stream, get_handle, system_fields
 
 
 def analytic_spec(system, **fields) -> NetworkSpec:
     """The NetworkSpec of a parameter-free trial state (Laughlin, Jain, MooreRead, Halperin): no network
     dimensions, the sphere and the interaction from ``system``, the state's own fields as keywords."""
-    radius = getattr(system, "radius", None) if system is not None else None
-    lam = getattr(system, "interaction_strength", 1.0) if system is not None else 1.0
-    itype = getattr(system, "interaction_type", "coulomb") if system is not None else "coulomb"
-    return NetworkSpec(
-        ndets=1, num_heads=1, heads_dim=4, num_layers=0,
-        radius=radius, interaction_strength=float(lam), interaction_type=str(getattr(itype, "value", itype)),
-        **fields,
-    )
+    return NetworkSpec(ndets=1, num_heads=1, heads_dim=4, num_layers=0, **system_fields(system), **fields)
 
 
 class Laughlin(Psiformer):

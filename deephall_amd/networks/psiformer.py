@@ -19,6 +19,7 @@ it on the device) and manages the per-device handle and workspace.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import functools
 import os
 import math
@@ -62,6 +63,9 @@ class NetworkSpec:
     halperin: tuple | None = None  # halperin: (m_up, m_dn, n) ints, the arguments of dh_create_halperin
     # quasihole: (base, (m_up, m_dn, n), p, ((theta, phi, kind), ...)), the fields of dh_quasihole
     quasihole: tuple | None = None
+    # config.Impurity entries of the Hamiltonian's one-body term (hamiltonian._run_local_energy adds it
+    # after dh_local_energy); they never enter a handle: to_c and get_handle leave them out
+    impurities: tuple = ()
 
     @property
     def nelec(self) -> int:
@@ -113,6 +117,18 @@ class NetworkSpec:
         if self.quasihole is not None:
             return lib.dh_create_quasihole(C.byref(cfg), C.byref(self.quasihole_c()), C.byref(handle))
         return lib.dh_create(C.byref(cfg), C.byref(handle))
+
+
+def system_fields(system) -> dict:
+    """The NetworkSpec fields every network builder reads from ``system`` (None: the defaults):
+    radius, interaction_strength, interaction_type and impurities."""
+    itype = getattr(system, "interaction_type", "coulomb")
+    return dict(
+        radius=getattr(system, "radius", None),
+        interaction_strength=float(getattr(system, "interaction_strength", 1.0)),
+        interaction_type=str(getattr(itype, "value", itype)),
+        impurities=tuple(getattr(system, "impurities", ()) or ()),
+    )
 
 
 class NativeHandle:
@@ -190,6 +206,8 @@ def get_handle(spec: NetworkSpec, device) -> NativeHandle:
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("deephall_amd runs on the GPU only (no CPU fallback): pass CUDA/HIP tensors")
+    if spec.impurities:  # not a handle's business: specs that differ in them alone share one
+        spec = dataclasses.replace(spec, impurities=())
     key = (spec, device.index if device.index is not None else torch.cuda.current_device())
     if key not in _HANDLES:
         _HANDLES[key] = NativeHandle(spec, torch.device("cuda", key[1]))
@@ -402,9 +420,6 @@ class Psiformer:
         self.orbital_type = str(getattr(orbital_type, "value", orbital_type))
         if self.orbital_type not in ("full", "sparse"):
             raise ValueError(f"unknown orbital type {self.orbital_type!r}")
-        radius = getattr(system, "radius", None) if system is not None else None
-        lam = getattr(system, "interaction_strength", 1.0) if system is not None else 1.0
-        itype = getattr(system, "interaction_type", "coulomb") if system is not None else "coulomb"
         self.spec = NetworkSpec(
             nspins=self.nspins,
             flux=int(round(2 * self.Q)),
@@ -413,9 +428,7 @@ class Psiformer:
             heads_dim=self.heads_dim,
             num_layers=self.num_layers,
             orbital_type=self.orbital_type,
-            radius=radius,
-            interaction_strength=float(lam),
-            interaction_type=str(getattr(itype, "value", itype)),
+            **system_fields(system),
         )
         self._flat_cache = {}
         self._epoch = 0
@@ -624,11 +637,10 @@ class Psiformer:
         h.set_params_ref(flat, key)
         return h
 
-    def with_system(self, radius=None, interaction_strength=None):
+    def with_system(self, radius=None, interaction_strength=None, impurities=None):
         """The same network with another sphere radius / interaction strength (what
-        make_local_kinetic_energy(f, Q, r) evaluates, hamiltonian.py:83)."""
-        import dataclasses as _dc
-
+        make_local_kinetic_energy(f, Q, r) evaluates, hamiltonian.py:83).  The impurities stay
+        unless others are given (() drops them)."""
         other = object.__new__(type(self))
         other.__dict__.update(self.__dict__)
         kw = {}
@@ -636,7 +648,9 @@ class Psiformer:
             kw["radius"] = float(radius)
         if interaction_strength is not None:
             kw["interaction_strength"] = float(interaction_strength)
-        other.spec = _dc.replace(self.spec, **kw)
+        if impurities is not None:
+            kw["impurities"] = tuple(impurities)
+        other.spec = dataclasses.replace(self.spec, **kw)
         other._flat_cache = {}
         return other
 

@@ -637,6 +637,45 @@ int dh_hole_logs(const dh_config* cfg, const dh_hole_configs* configs, const flo
 int dh_hole_gram(const double* L, int B, int n_configs, const double* shift, double* S, int32_t* nvalid,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Impurity potential and the density around an axis (impurity.hip): no handle -------------
+ * Walkers x[B][nelec][2] float32 (theta, phi), nelec = n_up + n_dn, the slots below n_up up.  All
+ * arithmetic in double on the upcast angles.  With R = radius, u = r_i . r_a the cosine of the
+ * angle between electron i and impurity a, and the squared chord c^2 = 2 R^2 (1 - u):
+ *   DH_IMPURITY_GAUSSIAN  U_a = strength exp(-c^2 / (2 width^2))
+ *   DH_IMPURITY_CHARGE    U_a = strength / sqrt(c^2 + width^2)   (a point charge at height width)
+ * species: DH_HOLE_BOTH, DH_HOLE_UP or DH_HOLE_DOWN, the electrons the impurity acts on.
+ *
+ * dh_impurity_check       the checks of the array alone, no device call: 0 <= n_imp <=
+ *                         DH_MAX_IMPURITIES, non-null when n_imp > 0, every field finite, width > 0,
+ *                         a known kind and species, 0 <= theta <= pi.
+ * dh_external_potential   ext[b] (float32) = sum_a sum_{i in species(a)} U_a(r_i); when e_l
+ *                         (dh_local_energy's [B][2]) is not null also e_l[b][0] = (float)((double)
+ *                         e_l[b][0] + the sum), e_l[b][1] untouched.  The impurities are a host array and
+ *                         reach the kernel by value; no device memory is allocated.  A fixed order and
+ *                         no float atomics: a walker's value is the same bits alone and in any batch.  A
+ *                         walker with a non-finite coordinate gives NaN in ext and in e_l[b][0].
+ * dh_axis_histogram       adds to counts[2][bins] (device, unsigned; row 0 up, row 1 down) the
+ *                         electrons by u = r_i . a, a the axis (axis_theta, axis_phi): bins of equal
+ *                         area, bin k is 1 - 2 (k + 1) / bins < u <= 1 - 2 k / bins, the last one
+ *                         closed at u = -1; NaN is dropped.  Integer atomics: two calls give the
+ *                         same bits.  The caller zeroes counts.
+ * Checked before any device call, DH_EINVAL with a message that starts "impurity:" otherwise:
+ * non-null pointers, B >= 1, n_up, n_dn >= 0, 1 <= nelec <= 32, B nelec < 2^31, radius finite and
+ * > 0, the impurities as dh_impurity_check, the axis finite with 0 <= axis_theta <= pi,
+ * 1 <= bins <= 4096. */
+#define DH_MAX_IMPURITIES 8
+#define DH_IMPURITY_GAUSSIAN 0
+#define DH_IMPURITY_CHARGE 1
+typedef struct dh_impurity {
+  double theta, phi, strength, width;
+  int kind, species;
+} dh_impurity;
+int dh_impurity_check(const dh_impurity* impurities, int n_imp);
+int dh_external_potential(const float* x, int B, int n_up, int n_dn, double radius, const dh_impurity* impurities,
+                          int n_imp, float* e_l, float* ext, void* stream);
+int dh_axis_histogram(const float* x, int B, int n_up, int n_dn, double axis_theta, double axis_phi, int bins,
+                      unsigned* counts, void* stream);
+
 /* ---- log psi supplied by the caller: the arbitrary-callable boundary ---------------------
  * The reference's make_mcmc_step(batch_network, ...) (mcmc.py:105-150) and
  * make_local_kinetic_energy(f, Q, r) (hamiltonian.py:83-172) accept ANY log psi.  For one
