@@ -123,6 +123,10 @@ EXPORTS = [
     "dh_impurity_check",
     "dh_external_potential",
     "dh_axis_histogram",
+    "dh_pair_workspace_bytes",
+    "dh_pair_displace",
+    "dh_pair_kernel",
+    "dh_pair_accumulate",
 ]
 
 DH_QUASIHOLE_MAX_HOLES = 8
@@ -361,6 +365,14 @@ def load(path: Path | str | None = None):
     lib.dh_rdm_displace.restype = i32
     lib.dh_rdm_accumulate.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]
     lib.dh_rdm_accumulate.restype = i32
+    lib.dh_pair_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.dh_pair_workspace_bytes.restype = sz
+    lib.dh_pair_displace.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
+    lib.dh_pair_displace.restype = i32
+    lib.dh_pair_kernel.argtypes = [vp, i32, i32, vp, vp]
+    lib.dh_pair_kernel.restype = i32
+    lib.dh_pair_accumulate.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+    lib.dh_pair_accumulate.restype = i32
     lib.dh_create_halperin.argtypes = [C.POINTER(DhConfig), i32, i32, i32, C.POINTER(vp)]
     lib.dh_create_halperin.restype = i32
     lib.dh_create_quasihole.argtypes = [C.POINTER(DhConfig), C.POINTER(DhQuasihole), C.POINTER(vp)]

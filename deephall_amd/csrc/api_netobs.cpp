@@ -1,7 +1,8 @@
 // The estimator calls of the C ABI (include/deephall_amd.h) that take no handle: they see walkers
-// and log psi values only.  Histograms, monopole orbitals, dh_swap_*, dh_rdm_*, dh_spin_*, dh_sf_*,
-// the hole overlap matrix, and the impurity potential with its axis histogram.  Every check comes
-// before any device call.
+// and log psi values only.  Histograms, monopole orbitals, dh_swap_*, dh_rdm_*, dh_pair_*, dh_spin_*,
+// dh_sf_*, the hole overlap matrix, and the impurity potential with its axis histogram.  Every
+// check comes before any device call.
+#include <algorithm>
 #include <cmath>
 
 #include "api_internal.h"
@@ -143,6 +144,60 @@ int dh_rdm_accumulate(const float* x, const float* r_prime, const float* logpsi,
   HIP_TRY(rdm_table(flux, levels, &table));
   HIP_TRY(launch_rdm_accumulate(x, r_prime, logpsi, logpsi_p, B, nelec, n_up, flux, levels, P, by_spin != 0, table,
                                 rho, nvalid, workspace, (hipStream_t)stream));
+  return check_launch();
+}
+
+// ---- pair amplitudes (pairamp.hip): no handle either ----
+
+namespace {
+const char* pair_size_error(int B, int nelec, int P) {
+  if (B < 1 || P < 1) return "pair: B < 1 or P < 1";
+  if (nelec < 1 || nelec > 32) return "pair: nelec outside 1..32";
+  if ((int64_t)P * B > (int64_t)1 << 30) return "pair: P B > 2^30";
+  if ((int64_t)P * B * std::max(1, nelec * (nelec - 1) / 2) > INT32_MAX)
+    return "pair: P B nelec (nelec - 1) / 2 >= 2^31";
+  return nullptr;
+}
+const char* pair_flux_error(int flux) {
+  return flux < 0 || flux > kPairMaxFlux ? "pair: flux outside 0..126" : nullptr;
+}
+}  // namespace
+
+size_t dh_pair_workspace_bytes(int B, int nelec, int flux, int P) {
+  if (pair_size_error(B, nelec, P) || pair_flux_error(flux)) return 0;
+  return align64(pair_workspace_bytes((int64_t)P * B, nelec, flux));
+}
+
+int dh_pair_displace(const float* x, const float* r1, const float* r2, int B, int nelec, int P, int pair0, int pair1,
+                     float* xp, void* stream) {
+  if (!x || !r1 || !r2 || !xp) return fail(DH_EINVAL, "pair: null pointer");
+  if (const char* e = pair_size_error(B, nelec, P)) return fail(DH_EINVAL, e);
+  if (pair0 < 0 || pair1 <= pair0 || pair1 > nelec * (nelec - 1) / 2)
+    return fail(DH_EINVAL, "pair: need 0 <= pair0 < pair1 <= nelec (nelec - 1) / 2");
+  launch_pair_displace(x, r1, r2, B, nelec, P, pair0, pair1, xp, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_pair_kernel(const float* points, int n, int flux, double* out, void* stream) {
+  if (!points || !out) return fail(DH_EINVAL, "pair: null pointer");
+  if (const char* e = pair_flux_error(flux)) return fail(DH_EINVAL, e);
+  if (n < 1 || (int64_t)n * (flux + 1) > INT32_MAX) return fail(DH_EINVAL, "pair: n < 1 or n (flux + 1) >= 2^31");
+  launch_pair_kernel(points, n, flux, out, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_pair_accumulate(const float* x, const float* r1, const float* r2, const float* logpsi, const float* logpsi_p,
+                       int B, int nelec, int n_up, int flux, int P, double* A, int32_t* nvalid, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  if (!x || !r1 || !r2 || !logpsi || !logpsi_p || !A || !nvalid || !workspace)
+    return fail(DH_EINVAL, "pair: null pointer");
+  if (const char* e = pair_size_error(B, nelec, P)) return fail(DH_EINVAL, e);
+  if (const char* e = pair_flux_error(flux)) return fail(DH_EINVAL, e);
+  if (n_up < 0 || n_up > nelec) return fail(DH_EINVAL, "pair: n_up outside 0..nelec");
+  if (workspace_bytes < dh_pair_workspace_bytes(B, nelec, flux, P))
+    return fail(DH_EINVAL, "pair: workspace smaller than dh_pair_workspace_bytes");
+  HIP_TRY(launch_pair_accumulate(x, r1, r2, logpsi, logpsi_p, B, nelec, n_up, flux, P, A, nvalid, workspace,
+                                 (hipStream_t)stream));
   return check_launch();
 }
 

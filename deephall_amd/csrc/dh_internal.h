@@ -385,6 +385,23 @@ void launch_spin_ratios(const float* logpsi, const float* logpsi_s, int B, int p
                         hipStream_t s);
 void launch_spin_reduce(const float* logpsi, int B, int n_up, int n_dn, void* workspace, double* s2, double* pairs,
                         double* total, int32_t* nvalid, hipStream_t s);
+// Pair amplitudes (pairamp.hip): the rows with the electrons of pair q = (i < j), lexicographic,
+// at r1[p][b] and r2[p][b]; (4 pi)^2 K_L of n quadruples; and A[3][flux + 1] complex, the sums over
+// the kept samples of the ratio times K_L by class (up-up, up-down, down-down).  The limits
+// (1 <= N <= 32, 0 <= flux <= kPairMaxFlux, P B <= 2^30, rows < 2^31, the pair window) are the callers' to check.
+constexpr int kPairMaxFlux = 126;
+constexpr int kPairMaxPairs = 32 * 31 / 2;
+struct PairSlots {
+  unsigned char i[kPairMaxPairs], j[kPairMaxPairs];
+};
+PairSlots pair_slots(int N);
+size_t pair_workspace_bytes(int64_t samples, int N, int flux);
+void launch_pair_displace(const float* x, const float* r1, const float* r2, int B, int N, int P, int pair0, int pair1,
+                          float* xp, hipStream_t s);
+void launch_pair_kernel(const float* points, int n, int flux, double* out, hipStream_t s);
+hipError_t launch_pair_accumulate(const float* x, const float* r1, const float* r2, const float* logpsi,
+                                  const float* logpsi_p, int B, int N, int n_up, int flux, int P, double* A,
+                                  int32_t* nvalid, void* workspace, hipStream_t s);
 // Static structure factor (sfactor.hip): per-walker pair sums T[B][3][lmax+1] (uu, ud, dd) of
 // P_L(cos gamma_ij) and multipoles rho[B][2][nlm] complex of Y_LM, and their sums over the valid
 // walkers reduced on the device in double.  The limits (nelec <= 32, 0 <= n_up <= nelec,

@@ -31,6 +31,11 @@ with the same names, options, value/state keys and digests:
   (observables/axis_density.py, not in the reference): equal-area bins of r_i . a, integer counts by
   species in csrc/impurity.hip (``dh_axis_histogram``); the axis can be one of ``system.impurities``,
   whose potential the adaptor's potential energy includes (``dh_external_potential``);
+* the pair amplitudes A_L, the mean number of pairs with pair angular momentum L in the lowest Landau
+  level (observables/pair_amplitude.py, not in the reference): the rows with two electrons displaced
+  and the reduction of the ratios times the pair projector over walkers, points and pairs in double
+  are csrc/pairamp.hip (``dh_pair_*``); pseudopotential.py turns A_L into the energy of any pair
+  interaction through its Haldane pseudopotentials on the host;
 * every wavefunction value goes through ``dh_logpsi`` (Psiformer or the native Laughlin
   state), the walk through ``dh_mcmc_step``;
 * ``evaluate`` is a minimal stand-in for NetObs's own evaluation loop (restore, burn-in,
@@ -42,8 +47,8 @@ with the same names, options, value/state keys and digests:
 from .adaptor import DeepHallAdaptor, DeepHallAuxData
 from .estimator import Estimator, Observable, evaluate
 from .hall_system import HallSystem
-from .observables import (axis_density, density, hole_overlap, ll_rdm, one_rdm, overlap, pair_corr, renyi2,
-                          spin_square, structure_factor)
+from .observables import (axis_density, density, hole_overlap, ll_rdm, one_rdm, overlap, pair_amplitude, pair_corr,
+                          renyi2, spin_square, structure_factor)
 
 
 class _Registry(dict):
@@ -75,6 +80,7 @@ EXTRA_ESTIMATORS = _Registry({
     "structure_factor": structure_factor.DEFAULT,
     "hole_overlap": hole_overlap.DEFAULT,
     "axis_density": axis_density.DEFAULT,
+    "pair_amplitude": pair_amplitude.DEFAULT,
 })
 
 # The own keys are the reference's ``deephall@`` names, so the registry still lists exactly what

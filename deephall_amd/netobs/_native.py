@@ -256,6 +256,85 @@ def rdm_ll_sums(apply, x: torch.Tensor, r_prime: torch.Tensor, n_up: int, flux: 
     return rdm_accumulate(x, r_prime, logpsi, torch.cat(parts), n_up, flux, levels, by_spin)
 
 
+# ---- pair amplitudes (csrc/pairamp.hip) -------------------------------------------------------------
+
+def _pair_points(x: torch.Tensor, r1: torch.Tensor, r2: torch.Tensor, who: str):
+    x, r1, r2 = _check_cuda(x), _check_cuda(r1), _check_cuda(r2)
+    B, N, _ = x.shape
+    P = r1.shape[0]
+    if r1.shape != (P, B, 2) or r2.shape != (P, B, 2):
+        raise ValueError(f"{who}: r1 and r2 must be [P, {B}, 2], got {tuple(r1.shape)}, {tuple(r2.shape)}")
+    return x, r1, r2, B, N, P
+
+
+def pair_displace(x: torch.Tensor, r1: torch.Tensor, r2: torch.Tensor, pair0: int = 0,
+                  pair1: int | None = None) -> torch.Tensor:
+    """xp[pair1 - pair0, P, B, N, 2]: xp[q - pair0, p, b] is walker b of x[B, N, 2] with electron i at
+    r1[p, b] and electron j at r2[p, b], q the pair (i < j) in lexicographic order.  pair1 None: all
+    N (N - 1) / 2 pairs."""
+    x, r1, r2, B, N, P = _pair_points(x, r1, r2, "pair_displace")
+    pair1 = N * (N - 1) // 2 if pair1 is None else int(pair1)
+    xp = torch.empty(max(pair1 - int(pair0), 0), P, B, N, 2, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().dh_pair_displace(_ptr(x), _ptr(r1), _ptr(r2), B, N, P, int(pair0), pair1, _ptr(xp),
+                                            _stream(x.device)))
+    return xp
+
+
+def pair_kernel(points: torch.Tensor, flux: int) -> torch.Tensor:
+    """(4 pi)^2 K_L(r1, r2; r1', r2'), L = 0..flux: complex128 [n, flux + 1] for points[n, 4, 2]."""
+    pts = _check_cuda(points)
+    n = pts.shape[0]
+    if pts.shape != (n, 4, 2):
+        raise ValueError(f"pair_kernel: points must be [n, 4, 2], got {tuple(pts.shape)}")
+    out = torch.empty(n, int(flux) + 1, 2, dtype=torch.float64, device=pts.device)
+    _lib.check(_lib.load().dh_pair_kernel(_ptr(pts), n, int(flux), _ptr(out), _stream(pts.device)))
+    return torch.view_as_complex(out)
+
+
+def pair_accumulate(x: torch.Tensor, r1: torch.Tensor, r2: torch.Tensor, logpsi: torch.Tensor, logpsi_p: torch.Tensor,
+                    n_up: int, flux: int):
+    """(A[3, flux + 1] complex128, nvalid): the SUM over the kept (walker, point) samples and the
+    up-up, up-down, down-down pairs of (4 pi)^2 K_L psi(R_{ij -> r1 r2}) / psi(R), from x[B, N, 2],
+    r1, r2 [P, B, 2], logpsi[B, 2] and logpsi_p[pairs P B, 2] float32 (dh_logpsi's layout; rows as
+    pair_displace orders them).  nvalid is read back from the device (one synchronisation)."""
+    x, r1, r2, B, N, P = _pair_points(x, r1, r2, "pair_accumulate")
+    logpsi, logpsi_p = _check_cuda(logpsi), _check_cuda(logpsi_p)
+    if logpsi.shape != (B, 2) or logpsi_p.shape != (N * (N - 1) // 2 * P * B, 2):
+        raise ValueError(f"pair_accumulate: shapes {tuple(logpsi.shape)}, {tuple(logpsi_p.shape)} do not fit x "
+                         f"{tuple(x.shape)} and {P} points")
+    lib = _lib.load()
+    nbytes = int(lib.dh_pair_workspace_bytes(B, N, int(flux), P))
+    if nbytes < 1:
+        raise ValueError(f"pair_accumulate: B = {B}, N = {N}, flux = {flux}, P = {P} outside B, P >= 1, 1 <= N <= 32, "
+                         "0 <= flux <= 126, P B <= 2^30, P B N (N - 1) / 2 < 2^31")
+    A = torch.empty(3, int(flux) + 1, 2, dtype=torch.float64, device=x.device)
+    nvalid = torch.empty(1, dtype=torch.int32, device=x.device)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+    if logpsi_p.numel() == 0:  # N = 1: no pair and no row, but the call wants a pointer
+        logpsi_p = logpsi
+    _lib.check(lib.dh_pair_accumulate(_ptr(x), _ptr(r1), _ptr(r2), _ptr(logpsi), _ptr(logpsi_p), B, N, int(n_up),
+                                      int(flux), P, _ptr(A), _ptr(nvalid), _ptr(ws), ws.numel() * 8,
+                                      _stream(x.device)))
+    return torch.view_as_complex(A), int(nvalid.item())
+
+
+def pair_amplitude_sums(apply, x: torch.Tensor, r1: torch.Tensor, r2: torch.Tensor, n_up: int, flux: int,
+                        max_rows: int | None = None):
+    """pair_accumulate's (A, nvalid) with the log-amplitudes from ``apply`` (complex log psi of
+    [rows, N, 2]): one call on x, then the displaced rows of whole pairs, at most ``max_rows`` rows
+    (and at least one pair) per call; None: all pairs in one call."""
+    x, r1, r2, B, N, P = _pair_points(x, r1, r2, "pair_amplitude_sums")
+    npairs = N * (N - 1) // 2
+    logpsi = _log_pairs(apply(x))
+    step = npairs if max_rows is None else max(1, int(max_rows) // (P * B))
+    parts = []
+    for q0 in range(0, npairs, max(step, 1)):
+        xp = pair_displace(x, r1, r2, q0, min(q0 + step, npairs))
+        parts.append(_log_pairs(apply(xp.reshape(-1, N, 2))))
+    logpsi_p = torch.cat(parts) if parts else torch.empty(0, 2, dtype=torch.float32, device=x.device)
+    return pair_accumulate(x, r1, r2, logpsi, logpsi_p, n_up, flux)
+
+
 # ---- static structure factor (csrc/sfactor.hip) ---------------------------------------------------
 
 def sf_nlm(lmax: int) -> int:

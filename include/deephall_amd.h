@@ -522,6 +522,47 @@ int dh_rdm_accumulate(const float* x, const float* r_prime, const float* logpsi,
                       int nelec, int n_up, int flux, int levels, int P, int by_spin, double* rho, int32_t* nvalid,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Pair amplitudes in the lowest Landau level ---------------------------------------------------
+ * A_L: the mean number of electron pairs with total pair angular momentum L = 0..flux (relative
+ * angular momentum m = flux - L).  Spinor of a point: u = cos(theta / 2) e^{i phi / 2},
+ * v = sin(theta / 2) e^{-i phi / 2}; <p|q> = u_p conj(u_q) + v_p conj(v_q).  For (r1, r2; r1', r2')
+ *   a = <1|1'><2|2'>,  b = <1|2'><2|1'>,  d = (u1 v2 - v1 u2) conj(u1' v2' - v1' u2') = a - b,
+ *   (4 pi)^2 K_L = n_L d^(flux - L) p_L,   p_0 = 1, p_1 = a + b,
+ *   L p_L = (2L - 1)(a + b) p_{L-1} - (L - 1) d^2 p_{L-2},
+ *   n_L = (flux + 1)^2 (2L + 1) / (flux + L + 1)  C(flux, L) / C(flux + L, L):
+ * the projector onto pair angular momentum L built from the orbitals Y_{Q,Q,m}, summed over M.
+ * Pairs q = (i < j) in lexicographic order, nelec (nelec - 1) / 2 of them.
+ *
+ * dh_pair_displace    xp[pair1 - pair0][P][B][nelec][2]: row ((q - pair0) P + p) B + b is walker b of
+ *                     x[B][nelec][2] with electron i at r1[p][b] and electron j at r2[p][b]
+ *                     (r1, r2 [P][B][2]), for the pairs pair0 <= q < pair1; copies of the floats.
+ * dh_pair_kernel      out[n][flux + 1][2] (re, im; double) = (4 pi)^2 K_L of the n quadruples
+ *                     points[n][4][2] = (r1, r2, r1', r2'), by the device function the accumulation
+ *                     uses; NaN for a quadruple with a non-finite coordinate.
+ * dh_pair_accumulate  OVERWRITES A[3][flux + 1][2] (re, im; double; up-up, up-down, down-down by the
+ *                     slots below n_up or from n_up on) with the SUM over the kept samples (b, p) and
+ *                     the pairs of the class of
+ *                       (4 pi)^2 K_L(x[b][i], x[b][j]; r1[p][b], r2[p][b])
+ *                         exp(logpsi_p[(q P + p) B + b] - logpsi[b]).
+ *                     logpsi[B][2] and logpsi_p[pairs P B][2] are float32 (re, im) as dh_logpsi
+ *                     writes them for x and for all of xp; the difference is exponentiated in
+ *                     double.  A sample is dropped whole when its own log, any of its pairs' logs or
+ *                     any ratio is not finite; nvalid (one device int32) = the number kept, so
+ *                     A / nvalid is the estimate.  A fixed order, no float atomics: two calls on
+ *                     the same inputs give identical bits.  workspace:
+ *                     dh_pair_workspace_bytes(B, nelec, flux, P) device bytes, 16-byte aligned.
+ * Checked before any device call, DH_EINVAL otherwise (the query then returns 0): 1 <= nelec <= 32,
+ * 0 <= flux <= 126, 0 <= n_up <= nelec, B >= 1, P >= 1, P B <= 2^30, P B nelec (nelec - 1) / 2 < 2^31, the pair
+ * window 0 <= pair0 < pair1 <= pairs, n >= 1, n (flux + 1) < 2^31, non-null pointers, the workspace
+ * size. */
+size_t dh_pair_workspace_bytes(int B, int nelec, int flux, int P);
+int dh_pair_displace(const float* x, const float* r1, const float* r2, int B, int nelec, int P, int pair0, int pair1,
+                     float* xp, void* stream);
+int dh_pair_kernel(const float* points, int n, int flux, double* out, void* stream);
+int dh_pair_accumulate(const float* x, const float* r1, const float* r2, const float* logpsi, const float* logpsi_p,
+                       int B, int nelec, int n_up, int flux, int P, double* A, int32_t* nvalid, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ---- Total spin: <S^2> by exchanging one up and one down electron ----------------------------
  * Walkers x[B][nelec][2]; the slots below n_up are up electrons (n_up + n_dn = nelec).  Pair
  * p = i n_dn + (j - n_up) of an up slot i and a down slot j, P = n_up n_dn pairs; R_p is the walker
