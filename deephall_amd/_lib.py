@@ -127,6 +127,8 @@ EXPORTS = [
     "dh_pair_displace",
     "dh_pair_kernel",
     "dh_pair_accumulate",
+    "dh_subspace_workspace_bytes",
+    "dh_subspace_accumulate",
 ]
 
 DH_QUASIHOLE_MAX_HOLES = 8
@@ -142,6 +144,7 @@ DH_AXIS_MAX_BINS = 4096
 DH_SWAP_MAX_ANGLES = 64
 DH_RDM_MAX_LEVELS = 4
 DH_SF_MAX_L = 64
+DH_SUBSPACE_MAX_STATES = 32
 
 DH_NFID = 5  # dh_fidelity_partial: m, S re, S im, S2, n
 
@@ -387,6 +390,10 @@ def load(path: Path | str | None = None):
     lib.dh_hole_logs.restype = i32
     lib.dh_hole_gram.argtypes = [vp, i32, i32, vp, vp, vp, vp, sz, vp]
     lib.dh_hole_gram.restype = i32
+    lib.dh_subspace_workspace_bytes.argtypes = [i32, i32]
+    lib.dh_subspace_workspace_bytes.restype = sz
+    lib.dh_subspace_accumulate.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.dh_subspace_accumulate.restype = i32
     pi = C.POINTER(DhImpurity)  # the impurities: a host array
     lib.dh_impurity_check.argtypes = [pi, i32]
     lib.dh_impurity_check.restype = i32

@@ -1,7 +1,7 @@
 // The estimator calls of the C ABI (include/deephall_amd.h) that take no handle: they see walkers
 // and log psi values only.  Histograms, monopole orbitals, dh_swap_*, dh_rdm_*, dh_pair_*, dh_spin_*,
-// dh_sf_*, the hole overlap matrix, and the impurity potential with its axis histogram.  Every
-// check comes before any device call.
+// dh_sf_*, the hole overlap matrix, the subspace matrices, and the impurity potential with its axis
+// histogram.  Every check comes before any device call.
 #include <algorithm>
 #include <cmath>
 
@@ -313,6 +313,33 @@ int dh_hole_gram(const double* L, int B, int n_configs, const double* shift, dou
   if (workspace_bytes < dh_hole_workspace_bytes(B, n_configs))
     return fail(DH_ENOMEM, "Holes: workspace smaller than dh_hole_workspace_bytes");
   launch_hole_gram(L, B, n_configs, shift, S, nvalid, workspace, (hipStream_t)stream);
+  return check_launch();
+}
+
+// ---- subspace matrices S, H, T of K states (subspace.hip): no handle either ----
+
+namespace {
+const char* subspace_error(int B, int K) {
+  if (B < 1) return "subspace: B < 1";
+  if (K < 1 || K > kSubspaceMaxStates) return "subspace: K outside 1..DH_SUBSPACE_MAX_STATES";
+  if ((int64_t)B * K > INT32_MAX) return "subspace: K B >= 2^31";
+  return nullptr;
+}
+}  // namespace
+
+size_t dh_subspace_workspace_bytes(int B, int K) {
+  if (subspace_error(B, K)) return 0;
+  return align64(subspace_workspace_bytes(B, K));
+}
+
+int dh_subspace_accumulate(const float* logs, const float* e_l, const float* ke, int B, int K, const double* shift,
+                           double* out, int32_t* nvalid, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!logs || !e_l || !ke || !shift || !out || !nvalid || !workspace)
+    return fail(DH_EINVAL, "subspace: null pointer");
+  if (const char* e = subspace_error(B, K)) return fail(DH_EINVAL, e);
+  if (workspace_bytes < dh_subspace_workspace_bytes(B, K))
+    return fail(DH_EINVAL, "subspace: workspace smaller than dh_subspace_workspace_bytes");
+  launch_subspace_accumulate(logs, e_l, ke, B, K, shift, out, nvalid, workspace, (hipStream_t)stream);
   return check_launch();
 }
 

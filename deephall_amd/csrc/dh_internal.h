@@ -553,6 +553,13 @@ size_t hole_workspace_bytes(int B, int K);
 void launch_hole_gram(const double* L, int B, int K, const double* shift, double* S, int32_t* nvalid, void* workspace,
                       hipStream_t s);
 
+// subspace.hip: the overlap, Hamiltonian and kinetic matrices of K states over the walkers
+// (dh_subspace_accumulate); logs, e_l, ke [K][B][2] float32, out [3][K][K][2] double
+constexpr int kSubspaceMaxStates = 32;  // = DH_SUBSPACE_MAX_STATES
+size_t subspace_workspace_bytes(int B, int K);
+void launch_subspace_accumulate(const float* logs, const float* e_l, const float* ke, int B, int K, const double* shift,
+                                double* out, int32_t* nvalid, void* workspace, hipStream_t s);
+
 // impurity.hip: the one-body impurity term of the local energy (dh_external_potential) and the
 // histogram of the angle from an axis (dh_axis_histogram).  The table is a kernel argument: unit
 // vectors and coefficients from the host, in double.  p, q: R^2 / w^2 and 0 (gaussian), 2 R^2 and

@@ -1,5 +1,5 @@
 // Device code shared by the estimator kernels (spin.hip, holes.hip, swap.hip, rdm.hip, fidelity.hip,
-// sfactor.hip).  Their convention, stated once: from the subtraction of two log psi on everything is
+// sfactor.hip, subspace.hip).  Their convention, stated once: from the subtraction of two log psi on everything is
 // double; every sum over walkers runs in a fixed order with no float atomics, so two calls give
 // identical bits; an invalid walker (a non-finite log or ratio) is NaN in the per-walker array and
 // skipped in the sums.  Nothing here adds a product to anything: each includer may contract a

@@ -36,6 +36,12 @@ with the same names, options, value/state keys and digests:
   and the reduction of the ratios times the pair projector over walkers, points and pairs in double
   are csrc/pairamp.hip (``dh_pair_*``); pseudopotential.py turns A_L into the energy of any pair
   interaction through its Haldane pseudopotentials on the host;
+* the energies in the span of K wavefunctions (observables/subspace.py, not in the reference): the
+  run's own network and up to 31 trial states on its walkers, one ``dh_local_energy`` call per state,
+  and the K x K overlap, Hamiltonian and kinetic matrices of their ratios and local energies summed
+  in double in csrc/subspace.hip (``dh_subspace_accumulate``); subspace.py Hermitises them, drops the
+  linearly dependent directions and solves H v = E S v on the host: an excitation spectrum (CF
+  excitons of each L from their determinants), and the same at another interaction strength;
 * every wavefunction value goes through ``dh_logpsi`` (Psiformer or the native Laughlin
   state), the walk through ``dh_mcmc_step``;
 * ``evaluate`` is a minimal stand-in for NetObs's own evaluation loop (restore, burn-in,
@@ -47,8 +53,10 @@ with the same names, options, value/state keys and digests:
 from .adaptor import DeepHallAdaptor, DeepHallAuxData
 from .estimator import Estimator, Observable, evaluate
 from .hall_system import HallSystem
+from . import subspace  # the host solver (netobs.subspace); the estimator is observables.subspace
 from .observables import (axis_density, density, hole_overlap, ll_rdm, one_rdm, overlap, pair_amplitude, pair_corr,
                           renyi2, spin_square, structure_factor)
+from .observables import subspace as subspace_estimator
 
 
 class _Registry(dict):
@@ -81,6 +89,7 @@ EXTRA_ESTIMATORS = _Registry({
     "hole_overlap": hole_overlap.DEFAULT,
     "axis_density": axis_density.DEFAULT,
     "pair_amplitude": pair_amplitude.DEFAULT,
+    "subspace": subspace_estimator.DEFAULT,
 })
 
 # The own keys are the reference's ``deephall@`` names, so the registry still lists exactly what

@@ -531,3 +531,33 @@ def hole_gram(L: torch.Tensor, shift: torch.Tensor | None = None):
     _lib.check(lib.dh_hole_gram(_ptr(Lr), B, K, _ptr(shift), _ptr(S), _ptr(nvalid), _ptr(ws), ws.numel() * 8,
                                 _stream(L.device)))
     return torch.view_as_complex(S), int(nvalid.item())
+
+
+# ---- subspace matrices of K states (csrc/subspace.hip) ---------------------------------------------
+
+def subspace_sums(logs: torch.Tensor, e_l: torch.Tensor, ke: torch.Tensor, shift: torch.Tensor | None = None):
+    """(out[3, K, K] complex128 on the device, nvalid): out[0] = S, out[1] = H, out[2] = T with
+    S[c, c'] = sum_b conj(r_c) r_c', H the same sum weighted by e_l[c', b], T by ke[c', b], over the walkers
+    whose inputs and ratios are all finite; r_c = exp(logs[c] - logs[0] - shift[c]).  logs, e_l, ke
+    [K, B, 2] float32 (re, im; dh_local_energy's layout, stacked by state), shift [K] real, None: zeros.
+    nvalid is read back from the device (one synchronisation)."""
+    logs, e_l, ke = _check_cuda(logs), _check_cuda(e_l), _check_cuda(ke)
+    if logs.dim() != 3 or logs.shape[2] != 2 or e_l.shape != logs.shape or ke.shape != logs.shape:
+        raise ValueError(f"subspace_sums: logs, e_l, ke must be [K, B, 2] alike, got {tuple(logs.shape)}, "
+                         f"{tuple(e_l.shape)}, {tuple(ke.shape)}")
+    K, B, _ = logs.shape
+    shift = (torch.zeros(K, dtype=torch.float64, device=logs.device) if shift is None
+             else torch.as_tensor(shift, dtype=torch.float64).to(logs.device).contiguous())
+    if shift.shape != (K,):
+        raise ValueError(f"subspace_sums: shift must be [{K}], got {tuple(shift.shape)}")
+    lib = _lib.load()
+    nbytes = int(lib.dh_subspace_workspace_bytes(B, K))
+    if nbytes < 1:
+        raise ValueError(f"subspace_sums: B = {B}, K = {K} outside B >= 1, 1 <= K <= {_lib.DH_SUBSPACE_MAX_STATES}, "
+                         "K B < 2^31")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=logs.device)
+    out = torch.empty(3, K, K, 2, dtype=torch.float64, device=logs.device)
+    nvalid = torch.empty(1, dtype=torch.int32, device=logs.device)
+    _lib.check(lib.dh_subspace_accumulate(_ptr(logs), _ptr(e_l), _ptr(ke), B, K, _ptr(shift), _ptr(out), _ptr(nvalid),
+                                          _ptr(ws), ws.numel() * 8, _stream(logs.device)))
+    return torch.view_as_complex(out), int(nvalid.item())

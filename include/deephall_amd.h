@@ -678,6 +678,31 @@ int dh_hole_logs(const dh_config* cfg, const dh_hole_configs* configs, const flo
 int dh_hole_gram(const double* L, int B, int n_configs, const double* shift, double* S, int32_t* nvalid,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Subspace matrices: overlap, Hamiltonian and kinetic energy of K states (subspace.hip) -----
+ * K wavefunctions on one set of B walkers, stacked by state c = 0 .. K - 1, state 0 the one the
+ * walkers sample.  All three inputs are float32 (re, im) pairs as dh_local_energy writes them:
+ *   logs[K][B][2]  log|psi_c| and arg psi_c    (obs columns 6, 7)
+ *   e_l[K][B][2]   the local energy of psi_c   (e_l)
+ *   ke[K][B][2]    its kinetic part            (obs columns 0, 1)
+ * and shift[K] is real (device, double, zeros allowed), as dh_hole_gram takes it.  With
+ * r_c(b) = exp(logs[c][b] - logs[0][b] - shift[c]), out[3][K][K][2] (re, im; double) holds
+ *   out[0] = S[c][c'] = sum_b conj(r_c) r_c'
+ *   out[1] = H[c][c'] = sum_b conj(r_c) r_c' e_l[c'][b]     (the operator acts on the ket)
+ *   out[2] = T[c][c'] = sum_b conj(r_c) r_c' ke[c'][b]
+ * over the valid walkers, and nvalid (one device int32) is their number.  A walker is valid when
+ * its 6 K inputs and its K ratios are all finite; an invalid one is dropped from every entry.
+ * Everything after the subtraction of the logs is double, the sums run in an order that depends on
+ * B and K alone, and there are no float atomics: two calls give identical bits.  H and T are not
+ * Hermitian on a finite sample; the caller Hermitises them.
+ * workspace: dh_subspace_workspace_bytes(B, K) device bytes, 16-byte aligned.  Checked before any
+ * device call, DH_EINVAL with a message that starts "subspace:" otherwise (the workspace query
+ * then returns 0): non-null pointers, B >= 1, 1 <= K <= DH_SUBSPACE_MAX_STATES, K B < 2^31, the
+ * workspace size.  No dh_handle, as for the swap kernels. */
+#define DH_SUBSPACE_MAX_STATES 32
+size_t dh_subspace_workspace_bytes(int B, int K);
+int dh_subspace_accumulate(const float* logs, const float* e_l, const float* ke, int B, int K, const double* shift,
+                           double* out, int32_t* nvalid, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Impurity potential and the density around an axis (impurity.hip): no handle -------------
  * Walkers x[B][nelec][2] float32 (theta, phi), nelec = n_up + n_dn, the slots below n_up up.  All
  * arithmetic in double on the upcast angles.  With R = radius, u = r_i . r_a the cosine of the
