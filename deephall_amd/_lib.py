@@ -95,6 +95,8 @@ EXPORTS = [
     "dh_ntk_jvp",
     "dh_fidelity_partial",
     "dh_fidelity_residual",
+    "dh_ortho_partial",
+    "dh_ortho_residual",
     "dh_swap_classify",
     "dh_swap_compact",
     "dh_swap_reduce",
@@ -147,6 +149,7 @@ DH_SF_MAX_L = 64
 DH_SUBSPACE_MAX_STATES = 32
 
 DH_NFID = 5  # dh_fidelity_partial: m, S re, S im, S2, n
+DH_ORTHO_MAX_STATES = 16
 
 
 PROF_KINDS = ["gemm", "attention", "layernorm", "input", "det_value", "det_energy", "mcmc",
@@ -349,6 +352,10 @@ def load(path: Path | str | None = None):
     lib.dh_fidelity_partial.restype = i32
     lib.dh_fidelity_residual.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.dh_fidelity_residual.restype = i32
+    lib.dh_ortho_partial.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.dh_ortho_partial.restype = i32
+    lib.dh_ortho_residual.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.dh_ortho_residual.restype = i32
     pf = C.POINTER(C.c_float)  # the cap angles: a host array
     lib.dh_swap_classify.argtypes = [vp, i32, i32, i32, i32, pf, i32, vp, vp, vp]
     lib.dh_swap_classify.restype = i32

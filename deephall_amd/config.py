@@ -271,6 +271,23 @@ class Pretrain:
 
 
 @dataclass
+class Orthogonal:
+    """Overlap penalties against frozen lower states, for excited states (orthogonal.py; not in the
+    reference): the energy phase minimises E + sum_k lambda_k F_k.  ``states``: () switches it off.
+    An entry is a trial state in the ``subspace`` estimator's form, ``{type: laughlin | jain |
+    pfaffian | halperin | quasihole, <sub-configs>}``, or a Psiformer checkpoint ``{checkpoint: <file
+    or directory>, psiformer: {...}?, orbital: ...?}``; either takes an optional ``penalty`` >= 0,
+    its lambda_k.  ``penalty``: lambda_k of the entries that name none; it should exceed the gap to
+    the state.  At most 16 states."""
+
+    states: tuple = ()
+    penalty: float = 1.0
+
+    def __post_init__(self):  # a list of dicts from a config file
+        self.states = tuple(dict(s) if isinstance(s, dict) else s for s in (self.states or ()))
+
+
+@dataclass
 class Optim:
     """config.py:160-165.  The default optimizer is KFAC, as in the reference
     (optimizers.py: make_kfac_training_step on the dh_kfac_* kernels)."""
@@ -281,6 +298,7 @@ class Optim:
     kfac: OptimizerKfac = field(default_factory=OptimizerKfac)
     minsr: OptimizerMinsr = field(default_factory=OptimizerMinsr)
     pretrain: Pretrain = field(default_factory=Pretrain)
+    orthogonal: Orthogonal = field(default_factory=Orthogonal)
 
 
 @dataclass

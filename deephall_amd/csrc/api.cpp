@@ -826,6 +826,23 @@ int dh_fidelity_residual(const float* logpsi, const float* logphi, int B, const 
   return check_launch();
 }
 
+int dh_ortho_partial(const float* logpsi, const float* logphi, int B, int K, double* part, void* stream) {
+  if (!logpsi || !logphi || !part) return fail(DH_EINVAL, "dh_ortho_partial: null argument");
+  if (B < 1) return fail(DH_EINVAL, "dh_ortho_partial needs B >= 1");
+  if (K < 1 || K > DH_ORTHO_MAX_STATES) return fail(DH_EINVAL, "dh_ortho_partial needs 1 <= K <= DH_ORTHO_MAX_STATES");
+  launch_ortho_partial(logpsi, logphi, B, K, part, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dh_ortho_residual(const float* logpsi, const float* logphi, int B, int K, const double* total,
+                      const double* weight, const float* e_l, float* out, void* stream) {
+  if (!logpsi || !logphi || !total || !weight || !out) return fail(DH_EINVAL, "dh_ortho_residual: null argument");
+  if (B < 1) return fail(DH_EINVAL, "dh_ortho_residual needs B >= 1");
+  if (K < 1 || K > DH_ORTHO_MAX_STATES) return fail(DH_EINVAL, "dh_ortho_residual needs 1 <= K <= DH_ORTHO_MAX_STATES");
+  launch_ortho_residual(logpsi, logphi, B, K, total, weight, e_l, out, (hipStream_t)stream);
+  return check_launch();
+}
+
 // Debug hook (tests only): run input + trunk + orbital GEMM for B walkers with
 // C = 1 (op 0) or 2N+5 (op 1) channels and leave the results in the workspace:
 // final trunk activations at float offset 0 ([rows][D]) and orbital features at

@@ -677,6 +677,11 @@ void launch_minsr_matrix(const float* T, const unsigned char* valid, int Bg, dou
 void launch_fidelity_partial(const float* logpsi, const float* logphi, int B, double* part, hipStream_t s);
 void launch_fidelity_residual(const float* logpsi, const float* logphi, int B, const double* total, float* resid,
                               hipStream_t s);
+// orthogonal.hip: dh_ortho_partial (part [K][DH_NFID] doubles, workgroup k = state k) and
+// dh_ortho_residual (e_l may be NULL)
+void launch_ortho_partial(const float* logpsi, const float* logphi, int B, int K, double* part, hipStream_t s);
+void launch_ortho_residual(const float* logpsi, const float* logphi, int B, int K, const double* total,
+                           const double* weight, const float* e_l, float* out, hipStream_t s);
 
 }  // namespace dh
 

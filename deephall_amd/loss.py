@@ -49,15 +49,20 @@ def device_stats(net, e_l, obs, n_accept=None, steps=1, penalties=False):
     return out
 
 
-def reduce_stats(local: torch.Tensor, raw: bool = False, flags=None):
+def reduce_stats(local: torch.Tensor, raw: bool = False, flags=None, extra=None):
     """One all-reduce of the packed device-local stats -> LossStats dict (0-d tensors).
     ``raw=True`` also returns the reduced packed vector (device, DH_STAT_* layout).
     ``flags``: host floats appended to the packed vector and averaged with it (the driver's
     checkpoint / signal decisions, so every rank acts on the same value); returned as
-    ``out["flags"]`` (device tensor, the mean over ranks)."""
+    ``out["flags"]`` (device tensor, the mean over ranks).
+    ``extra``: a second device vector that rides in the same all-reduce (the statistics of a
+    residual beside the energy's); returned as ``out["extra"]``, the mean over ranks."""
     local = local[:_NPACK]
     if flags:
         local = torch.cat([local, torch.tensor([float(f) for f in flags], dtype=local.dtype).to(local.device)])
+    nflag = local.numel()
+    if extra is not None:
+        local = torch.cat([local, extra.to(local.dtype)])
     g = constants.pmean(local)
     energy = torch.complex(g[0], g[1])
     out = {
@@ -72,7 +77,9 @@ def reduce_stats(local: torch.Tensor, raw: bool = False, flags=None):
         "pmove": g[11],
     }
     if flags:
-        out["flags"] = g[_NPACK:]
+        out["flags"] = g[_NPACK:nflag]
+    if extra is not None:
+        out["extra"] = g[nflag:]
     return (out, g) if raw else out
 
 
@@ -128,7 +135,15 @@ def make_loss_fn(network, system, mode: LossMode = LossMode.ENERGY_GRAD, curvatu
     ``(params, data) -> (e_l [B, 2], obs [B, 8])`` whose per-walker residual takes the local
     energy's place in everything that follows — statistics, centring and IQR clip (with no
     penalties and no handle), cotangents, VJP — and ``stats["fidelity"]`` is its
-    ``last_fidelity``.  None: the energy path, unchanged."""
+    ``last_fidelity``.  None: the energy path, unchanged.
+
+    A hook marked ``keeps_energy`` (orthogonal.make_orthogonal_residual) returns R = E_L minus
+    its penalty terms with the true ``obs`` and leaves the unpenalised ``(e_l, obs)`` in
+    ``last_energy``.  It keeps the network's handle and the system's lz / l2 penalties, as on
+    the energy path; every reported statistic is E_L's (a hook whose penalty is zero reports a
+    plain run's numbers), and only the centring of dh_loss_diff reads the statistics of R — one
+    more dh_energy_stats launch, both packed vectors in the one all-reduce.  ``stats`` also
+    carries the hook's ``last_fidelities`` and ``last_penalty`` as "fidelities" and "penalty"."""
     pen = (float(system.lz_penalty), float(system.lz_center), float(system.l2_penalty))
     penalties = pen[0] != 0.0 or pen[2] != 0.0
     if native_network(network) is None:
@@ -136,18 +151,34 @@ def make_loss_fn(network, system, mode: LossMode = LossMode.ENERGY_GRAD, curvatu
             raise TypeError("a residual hook needs a network of this library (Psiformer)")
         return _make_callable_loss_fn(network, system, mode, pen, penalties)
     net = resolve_network(network)
-    if residual is not None:
+    keeps = residual is not None and bool(getattr(residual, "keeps_energy", False))
+    if residual is not None and not keeps:
         pen, penalties = (0.0, 0.0, 0.0), False
-    snet = net if residual is None else None  # the statistics kernels' (unused) handle
+    snet = net if residual is None or keeps else None  # the statistics kernels' (unused) handle
+
+    def penalised(params, data, n_accept, steps, flags):
+        """The ``keeps_energy`` hook: (stats of E_L, reduced statistics of R, R, obs)."""
+        r, obs = residual(params, data)
+        e_l = residual.last_energy[0]
+        local = device_stats(snet, e_l, obs, n_accept, steps, penalties=penalties)
+        local_r = device_stats(snet, r, obs, None, 1, penalties=penalties)
+        stats = reduce_stats(local, flags=flags, extra=local_r[:_NPACK])
+        g = stats.pop("extra")
+        stats["fidelities"] = residual.last_fidelities
+        stats["penalty"] = residual.last_penalty
+        return stats, g, r, obs
 
     def loss_and_grad(params, data, n_accept=None, steps=1, flags=None):
         """``n_accept`` [B] int (mcmc_step(..., reduce=False).last_n_accept) puts pmove into
         the packed statistics; ``flags`` rides in the same all-reduce (reduce_stats)."""
-        e_l, obs = _run_local_energy(net, params, data) if residual is None else residual(params, data)
-        local = device_stats(snet, e_l, obs, n_accept, steps, penalties=penalties)
-        stats, g = reduce_stats(local, raw=True, flags=flags)
-        if residual is not None:
-            stats["fidelity"] = residual.last_fidelity
+        if keeps:
+            stats, g, e_l, obs = penalised(params, data, n_accept, steps, flags)
+        else:
+            e_l, obs = _run_local_energy(net, params, data) if residual is None else residual(params, data)
+            local = device_stats(snet, e_l, obs, n_accept, steps, penalties=penalties)
+            stats, g = reduce_stats(local, raw=True, flags=flags)
+            if residual is not None:
+                stats["fidelity"] = residual.last_fidelity
         loss_and_grad.last = (e_l, obs)
         diff, nvalid = loss_diff(snet, e_l, obs, g, *pen)
         if mode == LossMode.ENERGY_DIFF:

@@ -63,6 +63,10 @@ class NetworkSpec:
     halperin: tuple | None = None  # halperin: (m_up, m_dn, n) ints, the arguments of dh_create_halperin
     # quasihole: (base, (m_up, m_dn, n), p, ((theta, phi, kind), ...)), the fields of dh_quasihole
     quasihole: tuple | None = None
+    # None: every network of this spec shares one handle per device.  A string: a handle of its own
+    # (orthogonal.FrozenPsiformer, whose parameters then stay packed beside the trained network's);
+    # it never reaches the library
+    handle_tag: str | None = None
     # config.Impurity entries of the Hamiltonian's one-body term (hamiltonian._run_local_energy adds it
     # after dh_local_energy); they never enter a handle: to_c and get_handle leave them out
     impurities: tuple = ()

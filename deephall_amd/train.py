@@ -206,7 +206,14 @@ def train(cfg: Config):
     ``pretrain_stats.csv`` beside ``train_stats.csv``.  The energy minimisation then starts with
     a new optimizer state and its schedule at t = 0; walkers and MCMC width carry over.
     Pretraining is not resumable: a checkpoint restore skips it, and a run killed during it
-    starts it over.  With 0 iterations nothing here changes."""
+    starts it over.  With 0 iterations nothing here changes.
+
+    ``optim.orthogonal.states`` non-empty (not in the reference; orthogonal.py): the energy phase
+    minimises E + sum_k lambda_k F_k against the frozen states, which are rebuilt from the
+    configuration on every start, a checkpoint restore included, so the run is resumable.
+    Burn-in, the initial-energy line and pretraining are the plain ones.  ``train_stats.csv``
+    then ends in ``penalty`` and ``fidelity_0`` ... ``fidelity_{K-1}``; the energy columns stay
+    the unpenalised E_L's.  With no states nothing here changes."""
     from . import optimizers
     from .config import OptimizerName
     from .log import LogManager, init_logging
@@ -219,11 +226,17 @@ def train(cfg: Config):
         from . import pretrain as pre
 
         pre.make_reference(cfg)
+    ortho = None
+    if cfg.optim.orthogonal.states:  # likewise: host checks only, before any walker moves
+        from . import orthogonal
+
+        ortho = orthogonal.make_states(cfg)
     init_distributed()
     log_manager = LogManager(cfg)
     model = make_network(cfg.system, cfg.network)
     mcmc_step, pmoves = setup_mcmc(cfg, model)
-    opt_init, training_step = optimizers.make_optimizer_step(cfg, model)
+    residual = orthogonal.make_orthogonal_residual(model, *ortho) if ortho is not None else None
+    opt_init, training_step = optimizers.make_optimizer_step(cfg, model, residual=residual)
     key = PRNGKey(cfg.seed)
     steps = cfg.mcmc.steps
     device = torch.device("cuda", torch.cuda.current_device())
@@ -277,6 +290,10 @@ def train(cfg: Config):
                                                       cfg.mcmc.adapt_frequency, pmove, pmoves)
                 state = state._replace(mcmc_width=new_width)
                 energy = complex(stats["energy"].item())
+                more = {}
+                if residual is not None:
+                    more["penalty"] = f"{float(stats['penalty']):.6f}"
+                    more.update({f"fidelity_{k}": f"{f:.6f}" for k, f in enumerate(stats["fidelities"].tolist())})
                 writer.log(
                     step=str(step),
                     pmove=f"{pmove:.2f}",
@@ -288,6 +305,7 @@ def train(cfg: Config):
                     Lz=f"{float(stats['angular_momentum_z']):+.4f}",
                     Lz_square=f"{float(stats['angular_momentum_z_square']):.4f}",
                     L_square=f"{float(stats['angular_momentum_square']):.4f}",
+                    **more,
                 )
                 nan = bool(np.isnan(energy.real))
                 if ((time_due and (step + 1) % cfg.log.save_step_interval == 0)

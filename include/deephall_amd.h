@@ -424,6 +424,27 @@ int dh_fidelity_partial(const float* logpsi, const float* logphi, int B, double*
 int dh_fidelity_residual(const float* logpsi, const float* logphi, int B, const double* total, float* resid,
                          void* stream);
 
+/* Overlap penalty against K frozen lower states phi_k (excited-state training; not in the
+ * reference).  logpsi [B][2], logphi [K][B][2] float32 (device); the rules are dh_fidelity_*'s,
+ * per state: walker b is valid for state k when its four floats there are finite, the shift is
+ * m_k = max Re d_k over those walkers, the sums run in one fixed order with no atomics.
+ * dh_ortho_partial writes part[K][DH_NFID] doubles in one launch, one workgroup per state; row k
+ *   is bit for bit dh_fidelity_partial(logpsi, logphi[k]).  Rows of shards combine as that
+ *   call's partials do, state by state.
+ * dh_ortho_residual writes out[B][2] = (e_l ? e_l[b] : 0) - sum_k weight[k] (1 - n_k z_kb / S_k)
+ *   from the (combined) totals total[K][DH_NFID] and weight[K] doubles (device; lambda_k F_k):
+ *   double arithmetic, k ascending, the quotient as dh_fidelity_residual forms it, each product
+ *   weight[k] eps_kb rounded before it is subtracted, the result rounded once to float32.  A
+ *   walker invalid for any k is NaN; any k with n_k = 0, S_k = 0 or a non-finite weight makes
+ *   every output NaN.  With K = 1, weight 1 and e_l NULL the output is minus dh_fidelity_residual's;
+ *   with every weight 0 and every walker valid it is e_l.
+ * K outside 1 .. DH_ORTHO_MAX_STATES, B < 1 or a null pointer (e_l excepted) is DH_EINVAL before
+ * any device call. */
+#define DH_ORTHO_MAX_STATES 16
+int dh_ortho_partial(const float* logpsi, const float* logphi, int B, int K, double* part, void* stream);
+int dh_ortho_residual(const float* logpsi, const float* logphi, int B, int K, const double* total,
+                      const double* weight, const float* e_l, float* out, void* stream);
+
 /* Potential energy only (make_potential, hamiltonian.py:63-80), NOT multiplied by
  * interaction_strength: pe[B]. */
 int dh_potential(dh_handle* h, const float* x, int B, float* pe, void* stream);
